@@ -19,12 +19,21 @@ added); at N >= 2 every rank runs one shard.  The total work is the same at ever
 --workload C3 (1M nodes, one shard per GPU) is kept for kernel A/B work.
 
 The timed window of a shard starts after W warm-up ticks from t = 10 s and covers K ticks of
-steady-state gossip; inputs are resident in HBM before it starts.
+steady-state gossip; inputs are resident in HBM before it starts.  The untimed ramp before it is
+kept short: the few earlier generations of ids that recur in the slice are replayed just before
+it (gossip.workloads.compress_ramp; the same counters as at their real times).
 `value` = edge events processed by all shards / (max over ranks of the rank's summed timed
 windows).
 
-The rank-0 N=1 run also times ORACLE A (the reference's P2PNode logic on one CPU core,
-event-driven, unordered_set seen-sets) on a bounded sample of the same workload.
+A plain run sets up, warms up, times the K ticks and prints the result line (its roofline block
+is derived from the timed run's own counters).  --dump-outputs DIR also writes what the timed
+path computed by its last tick -- the per-node counters Engine.stats() returns, summed over the
+share shards -- as DIR/<name>.npy (float64; above 2^19 nodes a fixed, seeded sample of the nodes,
+listed in DIR/sample_nodes.npy).  The inputs depend only on the arguments.
+
+--full: the rank-0 N=1 run also times ORACLE A (the reference's P2PNode logic on one CPU core,
+event-driven, unordered_set seen-sets) and ORACLE B (bit-sliced, all cores) on a bounded sample
+of the same workload.
 """
 import argparse
 import json
@@ -81,6 +90,40 @@ CAPACITY_CODES = (-3, -5)  # GOSSIP_ENOMEM, GOSSIP_ECAPACITY
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+OUTPUT_NAMES = ("gen", "recv", "fwd", "sent", "processed", "peers", "sockets")  # gossip.Stats
+OUTPUT_SAMPLE = 1 << 19  # nodes written by --dump-outputs (8 arrays x 4 MiB)
+OUTPUT_SEED = 20240
+
+
+def output_nodes(n):
+    """The nodes whose counters --dump-outputs writes: all of them up to OUTPUT_SAMPLE, above that
+    a fixed sample (Philox, OUTPUT_SEED) in ascending order."""
+    if n <= OUTPUT_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.Generator(np.random.Philox(OUTPUT_SEED))
+    return np.sort(rng.choice(n, size=OUTPUT_SAMPLE, replace=False)).astype(np.int64)
+
+
+def sample_stats(st, nodes):
+    return gossip.Stats(*(getattr(st, k)[nodes].astype(np.uint64) for k in OUTPUT_NAMES))
+
+
+def add_stats(a, b):
+    """Counters of two share shards: the additive ones add exactly (gossip.dist.ADDITIVE), peers and
+    sockets belong to the graph."""
+    if a is None:
+        return b
+    return gossip.Stats(*(getattr(a, k) + getattr(b, k) if k not in ("peers", "sockets") else getattr(a, k)
+                          for k in OUTPUT_NAMES))
+
+
+def dump_outputs(path, st, nodes):
+    os.makedirs(path, exist_ok=True)
+    for k in OUTPUT_NAMES:
+        np.save(os.path.join(path, f"{k}.npy"), getattr(st, k).astype(np.float64))
+    np.save(os.path.join(path, "sample_nodes.npy"), nodes.astype(np.float64))
 
 
 def pmc_traffic(name, line, variant):
@@ -173,8 +216,10 @@ def young_breakdown(acc, launches, n):
     }
 
 
-def run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank, flags):
-    """Warm up and time every shard this rank owns; raises gossip.GossipError on failure."""
+def run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank, flags, out_nodes=None):
+    """Warm up and time every shard this rank owns; raises gossip.GossipError on failure.  With
+    out_nodes, acc["outputs"] holds those nodes' counters after the last timed tick, summed over
+    the rank's shards."""
     W, K = args.warmup, args.steps
     slice_tick = SLICE_NS // L_NS
     acc = dict(elapsed=0.0, edges=0, gens=0, launches=0, pull_ms=0.0, moved=0, dense=0, pe=0,
@@ -183,12 +228,14 @@ def run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank, fl
                young_fb=0, phase_ms=0.0)
     for s in my_shards:
         t_eng = time.perf_counter()
-        eng = gossip.Engine(wl["nodes"], L_NS, T0_NS, T_CUT_NS, device=local, flags=flags,
+        eng = gossip.Engine(wl["nodes"], L_NS, wl["t_start_ns"], T_CUT_NS, device=local, flags=flags,
                             shard_rank=s, shard_count=shards)
         acc["options"] = {k: option_or_none(eng, k) for k in LAUNCH_OPTIONS}
         try:
             eng.set_topology(topo)
+            t_topo = time.perf_counter()
             eng.set_schedule(ev)
+            t_sched = time.perf_counter()
             # ramp: every tick from the first generation of the slice schedule (LIFE ticks before
             # t = 10 s, plus the earlier floods of ids that recur in it) through W warm-up ticks
             eng.run(slice_tick + W)
@@ -205,8 +252,12 @@ def run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank, fl
                 dist.barrier()
             t1 = time.perf_counter()
             c1 = eng.counters()
+            if out_nodes is not None:
+                acc["outputs"] = add_stats(acc.get("outputs"), sample_stats(eng.stats(), out_nodes))
         finally:
+            t_close = time.perf_counter()
             eng.close()
+            t_closed = time.perf_counter()
         acc["elapsed"] += t1 - t0
         acc["edges"] += c1.edge_events - c0.edge_events
         acc["gens"] += c1.generations
@@ -243,7 +294,9 @@ def run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank, fl
         if rank == 0:
             log(f"[bench] shard {s} of {shards}: {c1.edge_events - c0.edge_events} edge events in "
                 f"{(t1 - t0) * 1e3:.1f} ms, window {c1.words_hw} words, ramp {c0.ticks} ticks, "
-                f"engine setup + ramp {t0 - t_eng:.1f} s")
+                f"engine setup + ramp {t0 - t_eng:.1f} s (graph {t_topo - t_eng:.1f}, schedule "
+                f"{t_sched - t_topo:.1f}, ramp {t0 - t_sched:.1f} with {c0.pull_phase_ms / 1e3:.1f} in "
+                f"{c0.pull_launches} pull phases), close {t_closed - t_close:.1f} s")
     return acc
 
 
@@ -256,7 +309,7 @@ def rehearse_rows(args, wl, topo, ev, shards, R, flags):
     the R - 1 other messages over xGMI.  Prints one JSON line marked REHEARSAL."""
     W, K = args.warmup, args.steps
     slice_tick = SLICE_NS // L_NS
-    eng = gossip.Engine(wl["nodes"], L_NS, T0_NS, T_CUT_NS, flags=flags, shard_rank=0, shard_count=shards)
+    eng = gossip.Engine(wl["nodes"], L_NS, wl["t_start_ns"], T_CUT_NS, flags=flags, shard_rank=0, shard_count=shards)
     try:
         eng.set_option("young", 0)
         eng.set_option("rehearse_rows", R)
@@ -335,7 +388,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="C4")
     ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baselines (ORACLE A on one core, ORACLE B on --threads) "
+                         "on a sample of the workload, after the timed ticks; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-node counters after the last timed tick to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=1, help="generations in the CPU sample")
     ap.add_argument("--cpu-hops", type=int, default=6, help="hops the CPU-sample floods run")
     ap.add_argument("--noskip", action="store_true",
@@ -359,6 +417,7 @@ def main():
                     help="diagnostic: one rank of an R-rank row partition of share shard 0 of "
                          "--rehearse-shards (default: the workload's fit) on this one GPU")
     args = ap.parse_args()
+    t_main = time.perf_counter()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -391,7 +450,12 @@ def main():
     W, K = args.warmup, args.steps
 
     t_setup = time.time()
-    topo = WL.topology(args.workload, nodes=n, threads=args.threads)
+    # (the graph is generated on a second thread while this one generates the schedule)
+    import threading
+    built = {}
+    th = threading.Thread(target=lambda: built.update(
+        topo=WL.topology(args.workload, nodes=n, threads=args.threads)))
+    th.start()
     # Steady-state slice of the reference's continuous run: the schedule is the reference's
     # (node RNGs from t = 0, ids counted from t = 5 s); the timed ticks start W ticks after
     # t = 10 s (tick 2000).  The engine replays every generation of the LIFE ticks before 10 s
@@ -399,7 +463,15 @@ def main():
     t_gen_end = SLICE_NS + (W + K + 1) * L_NS
     ev, sinfo = WL.slice_schedule(n, WL.CONFIGS[args.workload]["node_seed"], SLICE_NS, t_gen_end,
                                   threads=args.threads)
+    # The early generations (of ids that recur in the slice) move next to the slice and the engine
+    # starts there: the same counters without ~1,000 nearly empty ramp ticks (compress_ramp).
+    ev, wl["t_start_ns"] = WL.compress_ramp(ev, sinfo["t_lo_ns"])
+    th.join()
+    if "topo" not in built:
+        raise SystemExit("topology generation failed")
+    topo = built["topo"]
     flags = gossip.F_TIMING | (gossip.F_NOSKIP if args.noskip else 0)
+    out_nodes = output_nodes(n) if args.dump_outputs else None
 
     def shard_rule(shards):
         return resolve_shard_rule(args.shard_rule, shards)
@@ -431,11 +503,12 @@ def main():
             if rehearsal:  # one engine per rehearsed rank, in sequence (each its own timed window)
                 for s in my_shards:
                     rank_accs.append(run_shards(args, wl, topo, ev, [s], shards, dist, dev, local, rank,
-                                                flags | shard_flags(shard_rule(shards), args.fresh_tiles)))
+                                                flags | shard_flags(shard_rule(shards), args.fresh_tiles),
+                                                out_nodes))
                 acc = max(rank_accs, key=lambda a: a["elapsed"])  # the job waits for its slowest rank
             else:
                 acc = run_shards(args, wl, topo, ev, my_shards, shards, dist, dev, local, rank,
-                                 flags | shard_flags(shard_rule(shards), args.fresh_tiles))
+                                 flags | shard_flags(shard_rule(shards), args.fresh_tiles), out_nodes)
         except gossip.GossipError as e:
             if getattr(e, "code", None) not in CAPACITY_CODES:
                 raise
@@ -470,6 +543,15 @@ def main():
         want = int(np.count_nonzero(ev["ns"] < (SLICE_NS // L_NS + W + K) * L_NS))
         if int(gens_total) != want:
             raise SystemExit(f"shard coverage broken: {int(gens_total)} generations vs {want}")
+    if args.dump_outputs:
+        st = None
+        for a in (rank_accs if rehearsal else [acc]):  # (a rehearsal: the shards it ran)
+            st = add_stats(st, a["outputs"])
+        if dist:
+            st = gd.allreduce_stats(st, device=dev)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, st, out_nodes)
+            log(f"[bench] outputs of {len(out_nodes)} nodes written to {args.dump_outputs}")
 
     if rank == 0:
         avg_ms = pull_ms / max(launches, 1)
@@ -633,7 +715,7 @@ def main():
                 roof["traffic_note"] = why
         roof["pull_fraction_of_step"] = ((roof["avg_launch_ms"] * launches / 1e3) / elapsed) if elapsed > 0 else None
         out["roofline"] = roof
-        if n_gpus == 1 and world == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and world == 1 and not args.no_cpu_baseline:
             try:
                 win = ev[ev["ns"] >= SLICE_NS]
                 out["cpu_baseline"] = cpu_baseline(topo, win, args.cpu_sample, args.cpu_hops)
@@ -646,6 +728,8 @@ def main():
             except Exception as e:
                 out["cpu_baseline_bitsliced"] = {"value": None, "error": str(e)}
         print(json.dumps(out), flush=True)
+        log(f"[bench] {time.perf_counter() - t_main:.1f} s since start, "
+            f"{(W + K) * out['ms_per_step'] / 1e3:.1f} s of them in the {W} + {K} ticks")
     if dist:
         dist.destroy_process_group()
 

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <numeric>
 #include <queue>
@@ -671,6 +672,8 @@ inline uint32_t hint_stamp(int64_t t) { return 0x80u | hint_stamp1(t); }
 
 }  // namespace
 
+struct GraphDerived;  // host data derived from the graph alone, shared between engines (below)
+
 struct gossip_engine {
     gossip_config cfg{};
     int device = 0;
@@ -932,6 +935,7 @@ struct gossip_engine {
     int alloc_device();
     int prepare_instances();
     int compute_components();
+    GraphDerived& graph_derived(bool want_comp, bool want_ecc, bool want_rev);
     int tick_step(int64_t t);
     int tick_step_a(int64_t t);  // up to the tick's kernels (pull, births, snapshot counts)
     int tick_step_b(int64_t t);  // exchange (RCCL) + liveness read-back + bookkeeping
@@ -1079,8 +1083,105 @@ hipEvent_t gossip_engine::get_event() {
     return e;
 }
 
+// Host data derived from the graph alone: component labels, the flood-lifetime estimate (largest
+// BFS depth from four sample roots) and the reverse-edge index of the young tiles.  Share shards
+// run one engine after another over the same graph (10M nodes: several seconds each), so the last
+// graph's are kept, keyed by the CSR itself, and an engine whose CSR is equal takes them.
+struct GraphDerived {
+    std::vector<int64_t> rowptr;
+    std::vector<int32_t> col;
+    std::vector<uint32_t> comp;
+    int ecc = -1;
+    std::vector<int32_t> rev;
+    bool have_rev = false;
+};
+static std::mutex g_derived_mu;
+static GraphDerived g_derived;
+
+static int graph_ecc(uint32_t n, const std::vector<int64_t>& h_rowptr, const std::vector<int32_t>& h_col) {
+    const uint32_t roots[4] = {0u, n / 3u, (2u * n) / 3u, n - 1u};
+    int depth_of[4] = {0, 0, 0, 0};
+    std::vector<std::thread> ths;
+    for (int k = 0; k < 4; k++)
+        ths.emplace_back([&, k] {  // one BFS per root, each on its own thread
+            std::vector<int32_t> dist(n, -1);
+            std::vector<uint32_t> fr(1, roots[k]), nx;
+            dist[roots[k]] = 0;
+            int depth = 0;
+            while (!fr.empty()) {
+                nx.clear();
+                for (uint32_t u : fr)
+                    for (int64_t j = h_rowptr[u]; j < h_rowptr[u + 1]; j++) {
+                        const uint32_t w = (uint32_t)h_col[j];
+                        if (dist[w] < 0) {
+                            dist[w] = dist[u] + 1;
+                            nx.push_back(w);
+                        }
+                    }
+                if (!nx.empty()) depth++;
+                fr.swap(nx);
+            }
+            depth_of[k] = depth;
+        });
+    for (auto& t : ths) t.join();
+    return *std::max_element(depth_of, depth_of + 4);
+}
+
+// reverse edges: rev[j] = the entry of v in the list of u = col[j] (j in v's list)
+static std::vector<int32_t> graph_rev(uint32_t n, const std::vector<int64_t>& h_rowptr,
+                                      const std::vector<int32_t>& h_col) {
+    const uint64_t nnz = h_col.size();
+    std::vector<int32_t> rev(nnz, -1), perm(nnz);
+    const int th = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+    gossip::parallel_for(n, th, [&](uint64_t lo, uint64_t hi) {  // each row's entries by id
+        for (uint64_t u = lo; u < hi; u++) {
+            const int64_t b = h_rowptr[u], e = h_rowptr[u + 1];
+            for (int64_t j = b; j < e; j++) perm[j] = (int32_t)j;
+            std::sort(perm.begin() + b, perm.begin() + e,
+                      [&](int32_t x, int32_t y) { return h_col[x] < h_col[y]; });
+        }
+    });
+    gossip::parallel_for(n, th, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t v = lo; v < hi; v++)
+            for (int64_t j = h_rowptr[v]; j < h_rowptr[v + 1]; j++) {
+                const uint32_t u = (uint32_t)h_col[j];
+                auto b = perm.begin() + h_rowptr[u], e = perm.begin() + h_rowptr[u + 1];
+                auto it = std::lower_bound(b, e, (int32_t)v,
+                                           [&](int32_t x, int32_t val) { return h_col[x] < val; });
+                if (it != e && (uint32_t)h_col[*it] == v) rev[j] = *it;
+            }
+    });
+    return rev;
+}
+
+// The derived data of this engine's graph (g_derived_mu held by the caller): what is missing of
+// comp / ecc / rev is computed, the three at the same time.
+GraphDerived& gossip_engine::graph_derived(bool want_comp, bool want_ecc, bool want_rev) {
+    GraphDerived& d = g_derived;
+    if (d.rowptr != h_rowptr || d.col != h_col) {
+        d = GraphDerived();
+        d.rowptr = h_rowptr;
+        d.col = h_col;
+    }
+    std::vector<std::thread> ths;
+    if (want_comp && d.comp.empty() && n)
+        ths.emplace_back([&] { d.comp = gossip::components(n, h_rowptr.data(), h_col.data()); });
+    if (want_ecc && d.ecc < 0 && n)
+        ths.emplace_back([&] { d.ecc = graph_ecc(n, h_rowptr, h_col); });
+    if (want_rev && !d.have_rev)
+        ths.emplace_back([&] {
+            d.rev = graph_rev(n, h_rowptr, h_col);
+            d.have_rev = true;
+        });
+    for (auto& t : ths) t.join();
+    return d;
+}
+
 int gossip_engine::compute_components() {
-    if (comp.empty()) comp = gossip::components(n, h_rowptr.data(), h_col.data());
+    if (comp.empty()) {
+        std::lock_guard<std::mutex> g(g_derived_mu);
+        comp = graph_derived(true, false, false).comp;
+    }
     return GOSSIP_OK;
 }
 
@@ -1213,28 +1314,9 @@ int gossip_engine::alloc_device() {
         // over the CSR), plus the liveness read-back lag and slack.  Exceeding the estimate
         // is reported as GOSSIP_ECAPACITY, never silently truncated.
         int ecc = 0;
-        std::vector<int32_t> dist(n, -1);
-        std::vector<uint32_t> fr, nx;
-        const uint32_t roots[4] = {0u, n / 3u, (2u * n) / 3u, n - 1u};
-        for (uint32_t root : roots) {
-            std::fill(dist.begin(), dist.end(), -1);
-            fr.assign(1, root);
-            dist[root] = 0;
-            int depth = 0;
-            while (!fr.empty()) {
-                nx.clear();
-                for (uint32_t u : fr)
-                    for (int64_t j = h_rowptr[u]; j < h_rowptr[u + 1]; j++) {
-                        const uint32_t w = (uint32_t)h_col[j];
-                        if (dist[w] < 0) {
-                            dist[w] = dist[u] + 1;
-                            nx.push_back(w);
-                        }
-                    }
-                if (!nx.empty()) depth++;
-                fr.swap(nx);
-            }
-            ecc = std::max(ecc, depth);
+        {
+            std::lock_guard<std::mutex> g(g_derived_mu);
+            ecc = std::max(0, graph_derived(false, true, false).ecc);
         }
         // (the window widens itself if this is short: gossip_engine::grow)
         const int64_t life = ecc + kLag + 1;
@@ -1388,26 +1470,8 @@ int gossip_engine::alloc_device() {
             HIP_TRY(hipMemsetAsync(d_hint[k], 0, (size_t)nnz + 16, stream));  // stamps are >= 1
         }
         {  // reverse edges: rev[j] = the entry of v in the list of u = col[j] (j in v's list)
-            std::vector<int32_t> rev(nnz, -1), perm(nnz);
-            const int th = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-            gossip::parallel_for(n, th, [&](uint64_t lo, uint64_t hi) {  // each row's entries by id
-                for (uint64_t u = lo; u < hi; u++) {
-                    const int64_t b = h_rowptr[u], e = h_rowptr[u + 1];
-                    for (int64_t j = b; j < e; j++) perm[j] = (int32_t)j;
-                    std::sort(perm.begin() + b, perm.begin() + e,
-                              [&](int32_t x, int32_t y) { return h_col[x] < h_col[y]; });
-                }
-            });
-            gossip::parallel_for(n, th, [&](uint64_t lo, uint64_t hi) {
-                for (uint64_t v = lo; v < hi; v++)
-                    for (int64_t j = h_rowptr[v]; j < h_rowptr[v + 1]; j++) {
-                        const uint32_t u = (uint32_t)h_col[j];
-                        auto b = perm.begin() + h_rowptr[u], e = perm.begin() + h_rowptr[u + 1];
-                        auto it = std::lower_bound(b, e, (int32_t)v,
-                                                   [&](int32_t x, int32_t val) { return h_col[x] < val; });
-                        if (it != e && (uint32_t)h_col[*it] == v) rev[j] = *it;
-                    }
-            });
+            std::lock_guard<std::mutex> g(g_derived_mu);
+            const std::vector<int32_t>& rev = graph_derived(false, false, true).rev;
             HIP_TRY(hipMalloc(&d_rev, std::max<size_t>(nnz, 1) * 4));
             if (nnz) HIP_TRY(hipMemcpy(d_rev, rev.data(), nnz * 4, hipMemcpyHostToDevice));
         }
@@ -3998,6 +4062,15 @@ int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const goss
             e->last_birth_tick = e->ev.empty() ? e->tick0 : e->ev.back().ns / e->L;
             e->cut_tick = -1;  // per-column cut instead
             e->tick_end = e->last_birth_tick + 1;
+        }
+        {  // what prepare_instances and alloc_device will need of the graph's derived data, side by side
+            const bool coll = e->comp.empty() && gossip::any_id_collision(e->ev.size(), e->ev.data());
+            const bool may_young = !e->dense && !e->batch && !e->handshake && e->row_count == 1 &&
+                                   e->opt_rehearse_rows <= 1 && !(e->cfg.flags & GOSSIP_F_NOSKIP) &&
+                                   e->n < (1u << 31) &&
+                                   (e->opt_young == 1 || (e->opt_young == -1 && e->n >= (1u << 20)));
+            std::lock_guard<std::mutex> g(g_derived_mu);
+            e->graph_derived(coll, e->cfg.max_words == 0, may_young);
         }
         int rc = e->prepare_instances();
         if (rc) return rc;

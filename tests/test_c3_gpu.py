@@ -36,10 +36,10 @@ def c3(gossip):
     return topo, ev
 
 
-def _stats_at(gossip, topo, ev, ticks, **kw):
+def _stats_at(gossip, topo, ev, ticks, t_start_ns=None, **kw):
     """Per-node stats after each tick boundary in `ticks` (one engine run, stepped)."""
     W = _w()
-    eng = gossip.Engine(topo.num_nodes, W.L_NS, W.T0_NS, W.T_CUT_NS, **kw)
+    eng = gossip.Engine(topo.num_nodes, W.L_NS, W.T0_NS if t_start_ns is None else t_start_ns, W.T_CUT_NS, **kw)
     eng.set_topology(topo)
     eng.set_schedule(ev)
     out = []
@@ -70,6 +70,16 @@ def test_c3_slice_equals_continuous_run(gossip, c3):
     assert e1 - e0 == f1 - f0 > 0
     # the slice's ticks before the window are NOT the continuous run's (fewer floods in flight)
     assert int(b0.recv.sum()) < int(a0.recv.sum())
+    # the bench's compressed ramp (workloads.compress_ramp: the earlier generations of recurring
+    # ids moved next to the slice, the engine started there): every counter of the slice replay,
+    # at both ends of the timed window, not only the deltas
+    cs, t_start = W.compress_ramp(sl, info["t_lo_ns"])
+    assert t_start > W.T0_NS + 900 * W.L_NS and not np.array_equal(cs["ns"], sl["ns"])
+    (c0, g0), (c1, g1) = _stats_at(gossip, topo, cs, [t0, t1], t_start_ns=t_start)
+    assert (g0, g1) == (f0, f1)
+    for k in STATS:
+        assert np.array_equal(getattr(c0, k), getattr(b0, k)), k
+        assert np.array_equal(getattr(c1, k), getattr(b1, k)), k
 
 
 def test_c3_full_60s_invariants(gossip, c3):
