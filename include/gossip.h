@@ -75,7 +75,8 @@ uint32_t gossip_topology_num_nodes(const gossip_topology* t);
 uint64_t gossip_topology_num_links(const gossip_topology* t);
 /* Keys in std::map order. */
 int gossip_topology_get_links(const gossip_topology* t, uint32_t* a, uint32_t* b);
-/* Directed adjacency with multiplicity: CSR over distinct neighbours. */
+/* Peer lists with multiplicity: CSR over distinct neighbours.  Symmetric: a key (a,b) puts b in
+ * row a and a in row b, so an entry (v,u) always has its reverse (u,v). */
 uint64_t gossip_topology_num_entries(const gossip_topology* t);
 int gossip_topology_get_csr(const gossip_topology* t, int64_t* row_ptr, int32_t* col,
                             uint8_t* mult);
@@ -193,7 +194,12 @@ typedef struct gossip_config {
                                        use the same rule)                                        */
 
 int gossip_engine_create(const gossip_config* cfg, gossip_engine** out);
-/* Graph: CSR over distinct neighbours with multiplicity in {1,2} (see topology above). */
+/* Graph: CSR over distinct neighbours with multiplicity in {1,2} (see topology above).  The CSR
+ * must be symmetric -- link keys are undirected, and the pull, the hint stamps and the push marks
+ * all take a node's own list for both its senders and its readers: gossip_engine_set_graph returns
+ * GOSSIP_EINVAL naming the first entry (row v, col u) without a reverse entry (row u, col v), an
+ * O(nnz log deg) pass.  gossip_engine_set_topology skips that pass (a topology is symmetric by
+ * construction). */
 int gossip_engine_set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_ptr,
                             const int32_t* col, const uint8_t* mult);
 int gossip_engine_set_topology(gossip_engine* e, const gossip_topology* t);

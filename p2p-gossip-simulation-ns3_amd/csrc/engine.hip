@@ -3432,8 +3432,26 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
     }
 }
 
-int gossip_engine_set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_ptr,
-                            const int32_t* col, const uint8_t* mult) {
+// The pull walks a node's own list as its senders, and hint stamps (rev[]) and push marks reach a
+// writer's readers through the writer's list: every entry (v,u) needs its reverse (u,v).  Names the
+// first entry without one.  O(nnz log deg) on a sorted copy of the rows.
+static int check_symmetric(uint32_t n, const int64_t* row_ptr, const int32_t* col) {
+    std::vector<int32_t> sorted(col, col + row_ptr[n]);
+    for (uint32_t v = 0; v < n; v++) std::sort(sorted.begin() + row_ptr[v], sorted.begin() + row_ptr[v + 1]);
+    for (uint32_t v = 0; v < n; v++)
+        for (int64_t j = row_ptr[v]; j < row_ptr[v + 1]; j++) {
+            const uint32_t u = (uint32_t)col[j];
+            if (!std::binary_search(sorted.begin() + row_ptr[u], sorted.begin() + row_ptr[u + 1], (int32_t)v))
+                return set_error(GOSSIP_EINVAL, "asymmetric graph: entry " + std::to_string(j) + " (row " +
+                                                    std::to_string(v) + ", col " + std::to_string(u) +
+                                                    ") has no reverse entry (row " + std::to_string(u) +
+                                                    ", col " + std::to_string(v) + ")");
+        }
+    return GOSSIP_OK;
+}
+
+static int set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_ptr, const int32_t* col,
+                     const uint8_t* mult, bool check_symmetry) {
     if (!e || !row_ptr || (!col && row_ptr[num_nodes] > 0)) return set_error(GOSSIP_EINVAL, "NULL argument");
     if (e->have_graph) return set_error(GOSSIP_ESTATE, "graph already set");
     if (num_nodes != e->cfg.num_nodes) return set_error(GOSSIP_EINVAL, "num_nodes mismatch with config");
@@ -3465,6 +3483,8 @@ int gossip_engine_set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t*
             e->h_peers[v] = p;
             e->h_sockets[v] = (uint32_t)(row_ptr[v + 1] - row_ptr[v]);
         }
+        if (check_symmetry)
+            if (int rc = check_symmetric(num_nodes, row_ptr, col)) return rc;
     } catch (const std::bad_alloc&) {
         return set_error(GOSSIP_ENOMEM, "host allocation failed");
     }
@@ -3515,9 +3535,15 @@ int gossip_engine_set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t*
     return GOSSIP_OK;
 }
 
+int gossip_engine_set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_ptr,
+                            const int32_t* col, const uint8_t* mult) {
+    return set_graph(e, num_nodes, row_ptr, col, mult, true);
+}
+
 int gossip_engine_set_topology(gossip_engine* e, const gossip_topology* t) {
     if (!t) return set_error(GOSSIP_EINVAL, "NULL topology");
-    int rc = gossip_engine_set_graph(e, t->n, t->row_ptr.data(), t->col.data(), t->mult.data());
+    // (a topology's lists are symmetric by construction: no symmetry pass)
+    int rc = set_graph(e, t->n, t->row_ptr.data(), t->col.data(), t->mult.data(), false);
     if (rc) return rc;
     try {
         gossip::cached_topology_components(t, &e->comp);  // same graph: reuse the labels if built
