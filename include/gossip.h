@@ -290,8 +290,8 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  *                      k_transpose + k_dense_bits + k_dense_dedup            [GOSSIP_DENSE_FUSED]
  *   "young"            young-tile slots (k_pull_young): -1 auto (CSR tick engine, n >= 2^20),
  *                      0 off, 1 on (before the schedule)                    [GOSSIP_YOUNG]
- *   "young_age"        tiles stay in slots while their oldest shares are <= this many hops (5)
- *                                                                          [GOSSIP_YOUNG_AGE]
+ *   "young_age"        a tile's frontier is written to slots for this many ticks from its first birth
+ *                      (5: the frontiers of hops 0..4 of its oldest shares)   [GOSSIP_YOUNG_AGE]
  *   "young_cap"        slot entries per node before it falls back to dense rows (1..127)
  *                                                                          [GOSSIP_YOUNG_CAP]
  *   "pull_gate"        1: k_pull skips the own-seen loads of tiles no peer holds a row of (the
@@ -330,6 +330,15 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  *                      ticks old once they cover every bit it can still take (bottom-up early
  *                      exit); 0 = off, -1 = auto (1: every tile of a CSR pull; 0 in DENSE
  *                      mode, which gathers nothing)                          [GOSSIP_LATE_AGE]
+ *   "peer_order"       1: gossip_engine_set_graph / set_topology keep every peer list sorted by the
+ *                      peer's distinct-peer count, descending (ties: peer id ascending), so the
+ *                      early exit meets the peers likeliest to hold a share first (default), 0: the
+ *                      caller's order.  Before the graph only (GOSSIP_ESTATE after it)
+ *                                                                          [GOSSIP_PEER_ORDER]
+ *   "pull_batch"       k_pull tests the early exit once per batch of peer rows: 1: passes whose tiles
+ *                      hold a tile with a dense expected frontier (BFS layer model: at least half of
+ *                      its columns per row) gather first batches of 4 and 3 rows, then 6 at a
+ *                      time, 0: 6 at a time everywhere (default)              [GOSSIP_PULL_BATCH]
  *   "xchunks"          row partition: row chunks per tick of the pipelined exchange, 1..16 (4);
  *                      equal on every rank of a partition                    [GOSSIP_XCHUNKS]
  *   "rehearse_rows"    diagnostic, R >= 2 on an unpartitioned CSR engine (before the schedule;

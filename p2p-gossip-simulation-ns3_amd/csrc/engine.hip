@@ -141,6 +141,9 @@ struct PullArgs {
     // few nodes); this tick's rows of TM_PUSHW tiles mark their writer's peers in mark_next.
     const unsigned long long* mark_cur = nullptr;
     unsigned long long* mark_next = nullptr;
+    // 1: some listed tile of the tick is flagged TM_SHORT (option pull_batch): the launch runs the
+    // instantiation with the batch schedule (host only: the kernel's template flag says the same)
+    uint32_t short_batch = 0;
 };
 
 // Phase-ordered update of id groups inside one word (rare: only words holding groups).
@@ -259,6 +262,17 @@ void launch_pull_t(bool nt, uint32_t grid, size_t lds, hipStream_t s, const Pull
         if (pull_sp(LPW, EPN, a)) {
             // push marks in their own instantiation (the other one keeps its register allocation)
             const bool push = a.mark_cur != nullptr || a.mark_next != nullptr;
+            if (a.short_batch) {  // the batch schedule of exit-likely passes, its own instantiations too
+                if (nt && push)
+                    k_pull<LPW, 1, true, true, true, true><<<grid, 256, lds, s>>>(a);
+                else if (nt)
+                    k_pull<LPW, 1, true, true, false, true><<<grid, 256, lds, s>>>(a);
+                else if (push)
+                    k_pull<LPW, 1, false, true, true, true><<<grid, 256, lds, s>>>(a);
+                else
+                    k_pull<LPW, 1, false, true, false, true><<<grid, 256, lds, s>>>(a);
+                return;
+            }
             if (nt && push)
                 k_pull<LPW, 1, true, true, true><<<grid, 256, lds, s>>>(a);
             else if (nt)
@@ -848,7 +862,14 @@ struct gossip_engine {
     // a tile's F_next on few enough nodes that their peers are under kPushFrac of all), 0 off, 1 every
     // listed tile that is not dense-row (tests)
     int64_t opt_pull_push = -1;
-    std::vector<int64_t> tile_pushw;       // last tick k_pull marked the peers of the tile's row writers
+    // peer lists by degree (set_graph): 1 every row of the CSR sorted by the peer's distinct-peer
+    // count, descending (a high-degree peer is the likeliest to hold a share the node still wants,
+    // so k_pull's early exit fires after fewer rows), 0 the caller's order.  Before the graph only.
+    int64_t opt_peer_order = 1;
+    // k_pull's batch schedule on exit-likely passes (pull_kernel.h, TM_SHORT): 1 first batches of
+    // kShortB0 and kShortB1 rows where the pass's tiles hold a dense frontier, 0 kInflight always
+    int64_t opt_pull_batch = 0;
+    std::vector<int64_t> tile_pushw;      // last tick k_pull marked the peers of the tile's row writers
     // per tile (this life): (tick, generations) of the births that landed in it -- its frontier by
     // the layer model is the sum of their floods (an old tile can take a late generation of an id
     // instance it holds: one young flood among stragglers)
@@ -2175,6 +2196,7 @@ int gossip_engine::tick_step_a(int64_t t) {
     // push marks ride on the saturation words (an unmarked node's push tiles read as saturated)
     const bool push_on = sat_on && opt_pull_push != 0 && d_mark[0];
     bool pushw_any = false;
+    bool short_any = false;  // some listed tile is flagged TM_SHORT (option pull_batch)
     if (sat_used || dr_used) {
         if (TM_WORDS * ntw > tmask_cap) {
             HIP_TRY(hipStreamSynchronize(stream));
@@ -2219,6 +2241,15 @@ int gossip_engine::tick_step_a(int64_t t) {
                 for (uint32_t q = 0; q < kTileWords; q++) WF[tl * kTileWords + q] |= (uint8_t)WF_DW;
                 tile_dw[tl] = t;
                 dw = true;
+            }
+            // exit-likely (option pull_batch): the tile's F_cur rows -- the floods of its births, one
+            // tick ago -- are expected to hold at least half of its columns (a single-age tile: the
+            // layer model's hop_front of F_cur's hop), so most nodes are covered by their first rows.
+            // A misjudged tile costs round trips or rows, never results
+            if (opt_pull_batch && !fresh && tile_cols[tl] &&
+                frontier_entries(tl, t - 1) >= 0.5 * (double)tile_cols[tl]) {
+                m[TM_SHORT] |= bit;
+                short_any = true;
             }
             // push marks: the tile's F_cur rows were written by last tick's k_pull alone (listed then
             // with TM_PUSHW, no birth since) -> skipped at unmarked nodes; this tick's rows mark
@@ -2364,6 +2395,7 @@ int gossip_engine::tick_step_a(int64_t t) {
                 if (c.ptile && epn == 1 && (sat_used || dr_used)) {
                     c.tmask = d_tmask[slot];
                     c.sat = sat_used ? d_sat : nullptr;
+                    c.short_batch = short_any ? 1u : 0u;
                     if (push_on && pull_sp(lpw, epn, c)) {  // marks of last tick's push-write rows / this tick's
                         c.mark_cur = mark_tick == t - 1 ? d_mark[(t - 1) & 1] : nullptr;
                         mark_launches += c.mark_cur != nullptr;
@@ -3412,6 +3444,8 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
         e->opt_late_age = env_option("GOSSIP_LATE_AGE", -1);
         e->opt_pull_sat = env_option("GOSSIP_PULL_SAT", 1);
         e->opt_dense_rows = env_option("GOSSIP_DENSE_ROWS", -1);
+        e->opt_peer_order = env_option("GOSSIP_PEER_ORDER", 1) != 0 ? 1 : 0;
+        e->opt_pull_batch = env_option("GOSSIP_PULL_BATCH", 0) != 0 ? 1 : 0;
         e->trace = (cfg->flags & GOSSIP_F_TRACE) != 0;
         e->dense = cfg->mode == GOSSIP_MODE_DENSE;
         e->handshake = (cfg->flags & GOSSIP_F_HANDSHAKE) != 0;
@@ -3485,6 +3519,13 @@ static int set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_pt
         }
         if (check_symmetry)
             if (int rc = check_symmetric(num_nodes, row_ptr, col)) return rc;
+        // peer lists by degree (option peer_order), after the checks that name the caller's entries:
+        // everything derived from the graph (rev, hint bytes, components) reads h_col, and no CSR
+        // entry index ever goes back to the caller
+        if (e->opt_peer_order) {
+            const int th = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+            gossip::order_peers(num_nodes, e->h_rowptr.data(), e->h_col.data(), e->h_sockets.data(), th);
+        }
     } catch (const std::bad_alloc&) {
         return set_error(GOSSIP_ENOMEM, "host allocation failed");
     }
@@ -3492,7 +3533,7 @@ static int set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_pt
     HIP_TRY(hipMalloc(&e->d_col, std::max<size_t>(e->nnz, 1) * 4));
     HIP_TRY(hipMalloc(&e->d_deg, (size_t)std::max<uint32_t>(e->n, 1) * 4));
     HIP_TRY(hipMemcpy(e->d_rowptr, row_ptr, ((size_t)e->n + 1) * 8, hipMemcpyHostToDevice));
-    if (e->nnz) HIP_TRY(hipMemcpy(e->d_col, col, e->nnz * 4, hipMemcpyHostToDevice));
+    if (e->nnz) HIP_TRY(hipMemcpy(e->d_col, e->h_col.data(), e->nnz * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->d_deg, e->h_peers.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
     if (e->cfg.mode == GOSSIP_MODE_AUTO) e->dense = auto_dense(e->n, e->nnz, e->handshake);
     if (e->dense) {
@@ -3814,6 +3855,13 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
     } else if (k == "pull_push") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "pull_push: -1 (auto), 0 or 1");
         e->opt_pull_push = value;
+    } else if (k == "peer_order") {
+        if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "peer_order: 0 or 1");
+        if (e->have_graph) return set_error(GOSSIP_ESTATE, "peer_order: set before the graph");
+        e->opt_peer_order = value;
+    } else if (k == "pull_batch") {
+        if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "pull_batch: 0 or 1");
+        e->opt_pull_batch = value;
     } else if (k == "young_skip") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "young_skip: -1 (auto), 0 or 1");
         e->opt_young_skip = value;
@@ -3862,7 +3910,8 @@ int gossip_engine_get_option(const gossip_engine* e, const char* name, int64_t* 
         {"young_list_cap", e->opt_young_list_cap}, {"young_nt", e->opt_young_nt},
         {"young_skip", e->opt_young_skip}, {"pull_push", e->opt_pull_push}, {"young_idle", e->opt_young_idle}, {"young_grid", e->opt_young_grid}, {"mem_limit", e->opt_mem_limit}, {"late_age", e->opt_late_age},
         {"xchunks", e->opt_xchunks}, {"rehearse_rows", e->opt_rehearse_rows},
-        {"dense_fused", e->opt_dense_fused}, {"dense_min_tiles", e->opt_dense_min_tiles}};
+        {"dense_fused", e->opt_dense_fused}, {"dense_min_tiles", e->opt_dense_min_tiles},
+        {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch}};
     for (const auto& o : opts)
         if (k == o.first) {
             *value = o.second;

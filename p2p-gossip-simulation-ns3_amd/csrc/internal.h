@@ -59,6 +59,7 @@ bool cached_topology_components(const gossip_topology* t, std::vector<uint32_t>*
 bool any_id_collision(uint64_t m, const gossip_gen_event* ev);
 }
 
+#include <algorithm>
 #include <thread>
 namespace gossip {
 template <class F>
@@ -76,5 +77,17 @@ void parallel_for(uint64_t n, int threads, F&& f) {
         pool.emplace_back([&f, lo, hi] { f(lo, hi); });
     }
     for (auto& t : pool) t.join();
+}
+
+// Reorders every row of a CSR in place: peers by their distinct-peer count sockets[u], descending,
+// ties by peer id, ascending (engine option peer_order: the pull's early exit reads the peers most
+// likely to hold a share first).  Each row stays a permutation of itself.  Host only.
+inline void order_peers(uint32_t n, const int64_t* row_ptr, int32_t* col, const uint32_t* sockets, int threads) {
+    parallel_for(n, threads, [=](uint64_t lo, uint64_t hi) {
+        for (uint64_t v = lo; v < hi; v++)
+            std::sort(col + row_ptr[v], col + row_ptr[v + 1], [sockets](int32_t x, int32_t y) {
+                return sockets[x] != sockets[y] ? sockets[x] > sockets[y] : x < y;
+            });
+    });
 }
 }  // namespace gossip

@@ -111,10 +111,11 @@ __device__ __forceinline__ uint32_t group_add(uint32_t x, uint32_t lane) {
 //        read it without occupancy words: dense rows, above)
 enum : uint32_t { WF_CLEAR = 1u, WF_GROUP = 2u, WF_KEEP = 4u, WF_SNAP = 8u, WF_YOUNG = 16u, WF_LATE = 32u,
                   WF_DW = 64u, WF_BIRTH = 128u };  // WF_BIRTH: a generation lands in the word this tick (k_dense_fused)
-// PullArgs::tmask, per occupancy word tw: [5 tw] dense-row tiles (read without occupancy words),
-// [5 tw + 1] tiles whose sat bits are trusted this tick, [5 tw + 2] listed tiles that need occupancy,
-// [5 tw + 3] push tiles (skipped at unmarked nodes), [5 tw + 4] push-write tiles (rows mark peers)
-enum : uint32_t { TM_DENSE = 0, TM_SATOK = 1, TM_NZ = 2, TM_PUSH = 3, TM_PUSHW = 4, TM_WORDS = 5 };
+// PullArgs::tmask, per occupancy word tw: [6 tw] dense-row tiles (read without occupancy words),
+// [6 tw + 1] tiles whose sat bits are trusted this tick, [6 tw + 2] listed tiles that need occupancy,
+// [6 tw + 3] push tiles (skipped at unmarked nodes), [6 tw + 4] push-write tiles (rows mark peers),
+// [6 tw + 5] exit-likely tiles (their passes gather short first batches, PULL_SHORT_B0 below)
+enum : uint32_t { TM_DENSE = 0, TM_SATOK = 1, TM_NZ = 2, TM_PUSH = 3, TM_PUSHW = 4, TM_SHORT = 5, TM_WORDS = 6 };
 constexpr uint32_t kTmSlots = 16;  // LDS words for the launch's (<= 2) occupancy words of tmask
 
 constexpr uint32_t kPullLdsWords = 2048;  // words per launch: LDS liveness, new liveness, flags
@@ -125,6 +126,27 @@ constexpr uint32_t kPullLdsWords = 2048;  // words per launch: LDS liveness, new
 #define PULL_INFLIGHT 6
 #endif
 constexpr int kInflight = PULL_INFLIGHT;  // peer-row loads in flight per lane
+// Batch schedule of exit-likely passes (option pull_batch, tmask TM_SHORT): the early exit is tested
+// once per batch, so a pass whose tiles hold a dense frontier (most nodes are covered by their first
+// few peer rows) gathers a first batch of kShortB0 rows and a second of kShortB1, then kInflight at
+// a time; every other pass keeps kInflight throughout (a node that needs every peer row pays one
+// round trip per batch).  Never more than kInflight loads in flight.  A/B builds: make variants
+// C4 shard, degree-ordered peers, same box (profiles/r07/ab/): peer rows 198.3 GB per launch without
+// the schedule; 191.6 (5,3), 190.2 (4,4), 188.5 (4,3), 187.5 GB (4,2) with it, and 196.1 GB (5,3) when
+// only passes whose EVERY tile is flagged are short.  Phase time 57.00 ms without, 56.59 (4,3), 56.69
+// (4,2), 56.78 (4,4), 56.65-57.6 (5,3): the SHORT instantiation's spills (engine.hip launch_pull_t)
+// eat most of the rows saved, so the option is off by default
+#ifndef PULL_SHORT_B0
+#define PULL_SHORT_B0 4
+#define PULL_SHORT_B1 3
+#endif
+// a pass is short when ANY tile of it is flagged (0) or only when EVERY one is (1)
+#ifndef PULL_SHORT_EVERY
+#define PULL_SHORT_EVERY 0
+#endif
+constexpr int kShortB0 = PULL_SHORT_B0 < kInflight ? PULL_SHORT_B0 : kInflight;  // (never above the loads in flight)
+constexpr int kShortB1 = PULL_SHORT_B1 < kInflight ? PULL_SHORT_B1 : kInflight;
+static_assert(kShortB0 >= 1 && kShortB1 >= 1, "a batch holds a row");
 // Non-temporal row accesses: a template switch of k_pull<LPW,1>, chosen at launch by bitmap size
 // (engine.hip, kPullNtBytes).  On C4 (97 GB bitmaps) every row access non-temporal ran 128.6 ms
 // per launch against 132.1 ms; on C3 (2 GB bitmaps) 3.59 ms against 3.31 ms
@@ -184,9 +206,13 @@ __device__ __forceinline__ uint32_t pull_cid_load(const PullArgs& a, uint32_t st
 // flags instead of runtime ones (each runtime flag held a 64-bit SGPR mask; the kernel spilled
 // SGPRs into VGPR lanes, and every reload in the item loop is a VALU instruction)
 // PUSH (SP only): push marks on (PullArgs::mark_cur / mark_next; engine.hip launch_pull_t)
-template <int LPW, int EPN, bool NT = false, bool SP = false, bool PUSH = false>
+// SHORT (SP only): the batch schedule of exit-likely passes (tmask TM_SHORT, option pull_batch) -- its
+// own instantiation: the schedule's scalar state costs the item loop SGPR spills (65 -> 79), which
+// every launch without a flagged tile is spared
+template <int LPW, int EPN, bool NT = false, bool SP = false, bool PUSH = false, bool SHORT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1))) void k_pull(PullArgs a) {
     static_assert(SP || !PUSH, "push marks run in the SP instantiation");
+    static_assert(SP || !SHORT, "the batch schedule runs in the SP instantiation");
     const bool noskip = SP ? false : a.noskip != 0u;
     constexpr int GRP = LPW * EPN;  // lanes per node
     constexpr int NPW = 64 / GRP;   // nodes per wave step
@@ -240,10 +266,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
         const uint32_t p = threadIdx.x, np = a.nptile / TPP_;
         unsigned long long lm = 0ull;
         bool force = false, last = p + 1u == np;
+        bool sh_any = false, sh_all = true;  // the pass's tiles flagged exit-likely (TM_SHORT)
         if (p < np) {
             for (uint32_t k = 0; k < TPP_; k++) {
                 const uint32_t t = s_pt[p * TPP_ + k];
                 if (t == 0xffffu) continue;
+                if constexpr (SHORT) {
+                    const uint32_t tg = (a.wbase >> 4) + t;  // (its occupancy word: one of the launch's two)
+                    const uint32_t q = (tg >> 6) - (a.wbase >> 10);
+                    const bool sh = q < 2u && ((s_tm[q * TM_WORDS + TM_SHORT] >> (tg & 63u)) & 1ull) != 0ull;
+                    sh_any |= sh;
+                    sh_all &= sh;
+                }
                 unsigned long long lv = 0ull;
                 uint32_t fl = 0u;
                 for (uint32_t q = 0; q < 16u; q++) {
@@ -262,7 +296,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
         // the launch's occupancy words that hold a pass (bit q: tw_base + q)
         const unsigned long long tq = __ballot(p < np && ((a.wbase + (uint32_t)s_pt[p * TPP_] * 16u) >> 10) != (a.wbase >> 10));
         const unsigned long long t0 = __ballot(p < np && ((a.wbase + (uint32_t)s_pt[p * TPP_] * 16u) >> 10) == (a.wbase >> 10));
+        const unsigned long long shm = __ballot(p < np && (PULL_SHORT_EVERY ? sh_any && sh_all : sh_any));
         if (threadIdx.x == 0) {
+            if constexpr (SHORT) s_pforce[3] = (uint32_t)shm;  // passes with the short batch schedule
             s_pforce[0] = (uint32_t)fm;   // passes every node runs
             s_pforce[1] = (uint32_t)lmk;  // the last pass of each occupancy word (nodes with items)
             s_pforce[2] = (t0 ? 1u : 0u) | (tq ? 2u : 0u);
@@ -365,6 +401,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
                             a.sat[vj * a.ntw + tw_base + q] = s_satw[lane * 2u + q] & ~(PUSH ? s_psk[lane * 2u + q] : 0ull);
                 }
             }
+            // a step past the last node keeps a pass (all its items idle): next_item never sees an
+            // empty mask outside the PUSH instantiation, which skips such steps
+            if (!PUSH && vj >= n) m = s_pforce[0] | s_pforce[1];
             m = group_or<NPW>(m, lane);  // (the NPW nodes of a step are adjacent lanes)
             if (lane % NPW == 0u) s_sm[lane / NPW] = m;
             __builtin_amdgcn_wave_barrier();
@@ -546,12 +585,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
                     // rows, few unseen bits -- stop at the first batch that covers them all
                     const bool late = ((f0 | f1) & WF_LATE) != 0u;
                     // one lane group's worth of peers (ids in `cid`, occupancy words in `nzw`)
-                    auto gchunk = [&](uint32_t cid, unsigned long long nzw, int rem) {
+                    // (sh: the pass's short batch schedule, wave-uniform -- batches of kShortB0, kShortB1,
+                    // then kInflight rows)
+                    auto gchunk = [&](uint32_t cid, unsigned long long nzw, int rem, uint32_t sh) {
                         t_col += wave_count((int)gl < rem);
                         // the <= 8 occupancy bits of this pass's tiles, tested per lane by tile
                         // (a dense-row tile: every peer's row, whatever its occupancy word says)
                         const uint32_t nzp = pass_bits(nzw | drm, pass);
-                        for (int t0 = 0; t0 < rem; t0 += kInflight) {
+                        int bs = kInflight;
+                        for (int t0 = 0; t0 < rem; t0 += bs) {
+                            if constexpr (SHORT)
+                                bs = !sh ? kInflight : t0 == 0 ? kShortB0 : t0 == kShortB0 ? kShortB1 : kInflight;
+                            const int lim = SHORT ? min(rem, t0 + bs) : rem;
                             int open = (noskip || !late)
                                            ? 1 : (((want0 & ~acc0) | (want1 & ~acc1)) != 0ull);
                             open = (int)group_or<8>((uint32_t)open, lane);  // per tile (8 word-lanes)
@@ -569,7 +614,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
 #pragma unroll
                             for (int t = 0; t < kInflight; t++) {
                                 q[t] = make_ulonglong2(0ull, 0ull);
-                                const bool issue = open && tneed && t0 + t < rem && ((z[t] >> (wl >> 3)) & 1u);
+                                const bool issue = open && tneed && t0 + t < lim && ((z[t] >> (wl >> 3)) & 1u);
                                 if (issue) q[t] = load_row16<NT>(Fw + (uint64_t)u[t] * stride);
                                 t_pe += wave_count(issue);
                             }
@@ -583,7 +628,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
                     // the first lane group of peers is straight-line code (its ids and occupancy
                     // came with the previous item), so no loop header makes the wave wait for
                     // the loads this item just issued for the next ones
-                    gchunk(cid0, nz0, min(GRP, end - beg));
+                    // (uniform; s_pforce[3] is written with the pass masks: SP, <= 32 passes)
+                    const uint32_t shortp = SHORT ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((s_pforce[3] >> pass) & 1u)) : 0u;
+                    gchunk(cid0, nz0, min(GRP, end - beg), shortp);
                     for (int32_t cb = beg + GRP; cb < end; cb += GRP) {  // more peers (rare)
                         const int rem = min(GRP, end - cb);
                         const int32_t jj = cb + (int32_t)gl;
@@ -591,7 +638,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
                         const bool ld = (int)gl < rem && nz_needed(idx, tw);
                         const unsigned long long nzw = ld ? a.nz_cur[(uint64_t)cid * a.ntw + tw] : 0ull;
                         t_nz += wave_count(ld);
-                        gchunk(cid, nzw, rem);
+                        gchunk(cid, nzw, rem, 0u);
                     }
                 } else {
                     // edge-lane el walks peers beg+el, beg+el+EPN, ...; 8 in flight
