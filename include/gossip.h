@@ -339,6 +339,18 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  *                      hold a tile with a dense expected frontier (BFS layer model: at least half of
  *                      its columns per row) gather first batches of 4 and 3 rows, then 6 at a
  *                      time, 0: 6 at a time everywhere (default)              [GOSSIP_PULL_BATCH]
+ *   "seen_fold"        a tile that is read as dense rows and written whole (dense_rows), is no longer
+ *                      open and has every member of its id instances born carries its seen bits in
+ *                      its frontier rows: k_pull writes seen | new into F_next, writes no seen row, and
+ *                      reads the seen pair back from the node's own F_cur row the next tick; the tick
+ *                      the tile stops being written whole, nodes still unsaturated in it store their
+ *                      seen pair once.  -1 auto: on where allowed (pull_sat on, one engine, no
+ *                      handshake, hop batching, link timing, rehearse_rows, DENSE mode or
+ *                      GOSSIP_F_NOSKIP, and no tick with a keep mask so far; default), 0 off, 1 the
+ *                      same as auto.  Results are the same either way.  While a live tile has been
+ *                      folded, "pull_sat" 0 and "pull_tiles" 0 are refused (GOSSIP_EINVAL): the seen
+ *                      rows of its saturated nodes are stale behind their saturation bits
+ *                                                                          [GOSSIP_SEEN_FOLD]
  *   "xchunks"          row partition: row chunks per tick of the pipelined exchange, 1..16 (4);
  *                      equal on every rank of a partition                    [GOSSIP_XCHUNKS]
  *   "rehearse_rows"    diagnostic, R >= 2 on an unpartitioned CSR engine (before the schedule;
@@ -443,6 +455,8 @@ typedef struct gossip_counters {
     uint64_t pull_pushw_tiles;
     uint64_t pull_marks;
     uint64_t young_idle_ticks;   /* k_pull_young launches that skipped their idle nodes' walks (young_idle) */
+    uint64_t pull_fold_rows;     /* tile rows k_pull wrote folded -- seen | new in the F_next row, no seen
+                                    write -- since reset (option seen_fold) */
 } gossip_counters;
 int gossip_engine_get_counters(gossip_engine* e, gossip_counters* c);
 /* Option rehearse_rows = R: per row block r < R, summed since the last reset_timing -- pull time,

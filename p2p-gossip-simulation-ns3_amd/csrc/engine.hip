@@ -144,6 +144,9 @@ struct PullArgs {
     // 1: some listed tile of the tick is flagged TM_SHORT (option pull_batch): the launch runs the
     // instantiation with the batch schedule (host only: the kernel's template flag says the same)
     uint32_t short_batch = 0;
+    // 1: some tile of the launch carries TM_FOLDW or TM_SEENF (option seen_fold): the SP launch runs the
+    // instantiation that folds (host only, like short_batch)
+    uint32_t fold = 0;
 };
 
 // Phase-ordered update of id groups inside one word (rare: only words holding groups).
@@ -256,31 +259,32 @@ uint64_t pull_grid_cap(bool nt, int64_t ov) {
 constexpr int kWideLanes = 32;
 
 bool pull_sp(int lpw, int epn, const PullArgs& a);
+// the SP instantiations: push marks, the batch schedule of exit-likely passes and folded rows each in
+// instantiations of their own (the plain one keeps its register allocation)
+template <int LPW, bool SHORT, bool FOLD>
+void launch_pull_sp(bool nt, bool push, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    if (nt && push)
+        k_pull<LPW, 1, true, true, true, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+    else if (nt)
+        k_pull<LPW, 1, true, true, false, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+    else if (push)
+        k_pull<LPW, 1, false, true, true, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+    else
+        k_pull<LPW, 1, false, true, false, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+}
 template <int LPW, int EPN>
 void launch_pull_t(bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
     if constexpr (LPW == 32 && EPN == 1) {
         if (pull_sp(LPW, EPN, a)) {
-            // push marks in their own instantiation (the other one keeps its register allocation)
             const bool push = a.mark_cur != nullptr || a.mark_next != nullptr;
-            if (a.short_batch) {  // the batch schedule of exit-likely passes, its own instantiations too
-                if (nt && push)
-                    k_pull<LPW, 1, true, true, true, true><<<grid, 256, lds, s>>>(a);
-                else if (nt)
-                    k_pull<LPW, 1, true, true, false, true><<<grid, 256, lds, s>>>(a);
-                else if (push)
-                    k_pull<LPW, 1, false, true, true, true><<<grid, 256, lds, s>>>(a);
-                else
-                    k_pull<LPW, 1, false, true, false, true><<<grid, 256, lds, s>>>(a);
-                return;
-            }
-            if (nt && push)
-                k_pull<LPW, 1, true, true, true><<<grid, 256, lds, s>>>(a);
-            else if (nt)
-                k_pull<LPW, 1, true, true><<<grid, 256, lds, s>>>(a);
-            else if (push)
-                k_pull<LPW, 1, false, true, true><<<grid, 256, lds, s>>>(a);
+            if (a.short_batch && a.fold)
+                launch_pull_sp<LPW, true, true>(nt, push, grid, lds, s, a);
+            else if (a.short_batch)
+                launch_pull_sp<LPW, true, false>(nt, push, grid, lds, s, a);
+            else if (a.fold)  // some tile of the launch is folded or read back (TM_FOLDW, TM_SEENF)
+                launch_pull_sp<LPW, false, true>(nt, push, grid, lds, s, a);
             else
-                k_pull<LPW, 1, false, true><<<grid, 256, lds, s>>>(a);
+                launch_pull_sp<LPW, false, false>(nt, push, grid, lds, s, a);
             return;
         }
     }
@@ -858,6 +862,20 @@ struct gossip_engine {
     // bits written before a tick that listed the tile without them
     std::vector<int64_t> tile_satw;
     std::vector<int64_t> tile_dw;          // last tick every node's F_next row of the tile was written
+    // Seen bits carried in dense frontier rows (pull_kernel.h "folded rows"; option seen_fold): -1 auto
+    // (on where allowed), 0 off, 1 the same as auto
+    int64_t opt_seen_fold = -1;
+    std::vector<int64_t> tile_lastborn;    // latest birth tick of any member of any instance in the tile (this life)
+    std::vector<int64_t> tile_foldw;       // last tick k_pull wrote the tile's rows folded (TM_FOLDW)
+    std::vector<uint8_t> tile_folded;      // the tile was folded in this life: saturated nodes' seen rows are stale
+    bool fold_barred = false;              // a tick dropped receptions by a keep mask: peers' old bits are no longer safe
+    std::vector<uint8_t> fold_launch;      // per launch window of this tick: some tile carries TM_FOLDW / TM_SEENF
+    std::vector<uint8_t> tr_foldw, tr_seenf;  // per tile: this tick's TM_FOLDW / TM_SEENF (decode_trace)
+    bool any_folded() const {
+        for (size_t tl = 0; tl < tile_folded.size() && tl < tile_alloc.size(); tl++)
+            if (tile_alloc[tl] && tile_folded[tl]) return true;
+        return false;
+    }
     // push marks (pull_kernel.h, option pull_push): -1 auto (the BFS layer model expects the rows of
     // a tile's F_next on few enough nodes that their peers are under kPushFrac of all), 0 off, 1 every
     // listed tile that is not dense-row (tests)
@@ -1558,6 +1576,9 @@ int gossip_engine::alloc_device() {
     tile_listed.assign(stride / kTileWords, INT64_MIN);
     tile_satw.assign(stride / kTileWords, INT64_MIN);
     tile_dw.assign(stride / kTileWords, INT64_MIN);
+    tile_lastborn.assign(stride / kTileWords, INT64_MIN);
+    tile_foldw.assign(stride / kTileWords, INT64_MIN);
+    tile_folded.assign(stride / kTileWords, 0);
     tile_pushw.assign(stride / kTileWords, INT64_MIN);
     tile_births.assign(stride / kTileWords, {});
     tile_inj_prev.assign(stride / kTileWords, INT64_MIN);
@@ -1643,11 +1664,17 @@ int gossip_engine::grow(uint32_t new_stride) {
             d_nz[k] = q;
         }
         device_bytes += 16ull * n * (new_ntw - ntw);
-        for (unsigned long long** sp : {&d_sat}) {  // (a cache: zeros = nothing saturated)
-            if (!*sp) continue;
-            HIP_TRY(hipFree(*sp));
-            HIP_TRY(hipMalloc(sp, (size_t)n * new_ntw * 8));
-            HIP_TRY(hipMemset(*sp, 0, (size_t)n * new_ntw * 8));
+        // the sat rows are widened like the nz rows (new words: nothing saturated).  Not a cache any
+        // more: a node saturated in a folded tile (seen_fold) has a stale seen row behind its bit
+        if (d_sat) {
+            unsigned long long* q = nullptr;
+            HIP_TRY(hipMalloc(&q, (size_t)n * new_ntw * 8));
+            HIP_TRY(hipMemsetAsync(q, 0, (size_t)n * new_ntw * 8, stream));
+            HIP_TRY(hipMemcpy2DAsync(q, (size_t)new_ntw * 8, d_sat, (size_t)ntw * 8, (size_t)ntw * 8, n,
+                                     hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipFree(d_sat));
+            d_sat = q;
             device_bytes += 8ull * n * (new_ntw - ntw);
         }
         ntw = new_ntw;
@@ -1709,6 +1736,9 @@ int gossip_engine::grow(uint32_t new_stride) {
     tile_listed.resize(new_stride / kTileWords, INT64_MIN);
     tile_satw.resize(new_stride / kTileWords, INT64_MIN);
     tile_dw.resize(new_stride / kTileWords, INT64_MIN);
+    tile_lastborn.resize(new_stride / kTileWords, INT64_MIN);
+    tile_foldw.resize(new_stride / kTileWords, INT64_MIN);
+    tile_folded.resize(new_stride / kTileWords, 0);
     tile_pushw.resize(new_stride / kTileWords, INT64_MIN);
     tile_births.resize(new_stride / kTileWords);
     tile_inj_prev.resize(new_stride / kTileWords, INT64_MIN);
@@ -1765,6 +1795,9 @@ int gossip_engine::alloc_bits(uint32_t k, uint32_t* word, uint8_t* lo, int64_t t
         tile_listed[tl] = INT64_MIN;
         tile_satw[tl] = INT64_MIN;
         tile_dw[tl] = INT64_MIN;
+        tile_lastborn[tl] = INT64_MIN;
+        tile_foldw[tl] = INT64_MIN;
+        tile_folded[tl] = 0;
         tile_pushw[tl] = INT64_MIN;
         tile_births[tl].clear();
         for (uint32_t q = 0; q < kTileWords; q++) reset_now.push_back(tl * kTileWords + q);
@@ -1906,6 +1939,12 @@ int gossip_engine::tick_step_a(int64_t t) {
                 I.lo = l;
                 I.state = 1;
                 word_insts[w].push_back(ev_inst[q]);
+                // the tile's last expected birth (seen_fold: a tile folds only once every member is born)
+                int64_t& lb = tile_lastborn[w / kTileWords];
+                lb = std::max(lb, t);
+                if (I.nsrc > 1)
+                    for (uint32_t r = 0; r < I.nsrc; r++)
+                        lb = std::max(lb, (int64_t)(ev[grp_members[inst_moff[ev_inst[q]] + r]].ns / L));
                 if (I.nsrc > 1) {
                     const uint64_t gm = (I.nsrc >= 64 ? ~0ull : ((1ull << I.nsrc) - 1ull)) << l;
                     ctl[w].gmask |= gm;
@@ -2197,6 +2236,29 @@ int gossip_engine::tick_step_a(int64_t t) {
     const bool push_on = sat_on && opt_pull_push != 0 && d_mark[0];
     bool pushw_any = false;
     bool short_any = false;  // some listed tile is flagged TM_SHORT (option pull_batch)
+    // Folded rows (option seen_fold; pull_kernel.h): a sealed tile that is read dense and written whole
+    // this tick carries its seen bits in the F_next row (TM_FOLDW), and a tile folded last tick reads
+    // them back from F_cur (TM_SEENF).  Only where every tick is one hop of an unmasked, symmetric
+    // exchange on one engine (why peers may read folded rows), and never again once
+    // a keep mask has dropped receptions (a dropped column would come back out of a folded row).
+    if (keep_any) fold_barred = true;
+    const bool fold_ok = opt_seen_fold != 0 && sat_on && dr_used && !fold_barred && !handshake && !batch &&
+                         !link_timing && opt_rehearse_rows <= 1;
+    // does the launch over the window's words [wb, ..) keep sat bits (run_pull below: tile lists on
+    // the gathering kernel)?
+    auto sat_window = [&](uint32_t wb) {
+        const uint32_t wl = std::min(kPullLdsWords, hw - wb);
+        int lpw = 8;
+        while (lpw < 64 && 2 * lpw < (int)wl) lpw *= 2;
+        if (lpw == 64) return true;  // (a wide window: one peer walk per node)
+        const double avg_deg = n ? (double)nnz / n : 0.0;
+        return !(lpw * 2 <= 64 && 8 < avg_deg);  // (no edge-lanes)
+    };
+    if (trace) {
+        tr_foldw.assign(hw / kTileWords, 0);
+        tr_seenf.assign(hw / kTileWords, 0);
+    }
+    fold_launch.assign((hw + kPullLdsWords - 1) / kPullLdsWords, 0);
     if (sat_used || dr_used) {
         if (TM_WORDS * ntw > tmask_cap) {
             HIP_TRY(hipStreamSynchronize(stream));
@@ -2242,6 +2304,24 @@ int gossip_engine::tick_step_a(int64_t t) {
                 tile_dw[tl] = t;
                 dw = true;
             }
+            // folded rows: read back what last tick folded; fold again while the tile stays dense and
+            // sealed (not open, every member of every instance in it born before this tick)
+            const bool seenf = sat_used && tile_foldw[tl] == t - 1;
+            const bool sealed = (int64_t)tl != open_tile && tile_lastborn[tl] < t && tile_last_inject[tl] < t;
+            const bool foldw = fold_ok && dr && dw && sealed && sat_window(tl * kTileWords / kPullLdsWords * kPullLdsWords);
+            if (seenf) m[TM_SEENF] |= bit;
+            if (foldw) {
+                m[TM_FOLDW] |= bit;
+                tile_foldw[tl] = t;
+                tile_folded[tl] = 1;
+            }
+            if (seenf || foldw) {
+                fold_launch[tl * kTileWords / kPullLdsWords] = 1;
+                if (trace) {
+                    tr_foldw[tl] = foldw;
+                    tr_seenf[tl] = seenf;
+                }
+            }
             // exit-likely (option pull_batch): the tile's F_cur rows -- the floods of its births, one
             // tick ago -- are expected to hold at least half of its columns (a single-age tile: the
             // layer model's hop_front of F_cur's hop), so most nodes are covered by their first rows.
@@ -2275,6 +2355,10 @@ int gossip_engine::tick_step_a(int64_t t) {
             }
         HIP_TRY(hipMemcpyAsync(d_tmask[slot], TM, (size_t)TM_WORDS * ntw * 8, hipMemcpyHostToDevice, stream));
     }
+    if (!sat_used)  // (set_option refuses what would lead here)
+        for (uint32_t tl = 0; tl < hw / kTileWords; tl++)
+            if (tile_alloc[tl] && tile_foldw[tl] == t - 1)
+                return set_error(GOSSIP_ESTATE, "seen_fold: a tile's seen bits are in its frontier rows and this tick's pull keeps no saturation bits");
     // 5. upload + launches
     const uint32_t wact = hw;
     if (wact) HIP_TRY(hipMemcpyAsync(d_ctl[slot], C, (size_t)wact * sizeof(WordCtl), hipMemcpyHostToDevice, stream));
@@ -2396,6 +2480,7 @@ int gossip_engine::tick_step_a(int64_t t) {
                     c.tmask = d_tmask[slot];
                     c.sat = sat_used ? d_sat : nullptr;
                     c.short_batch = short_any ? 1u : 0u;
+                    c.fold = (sat_used && li < fold_launch.size() && fold_launch[li]) ? 1u : 0u;
                     if (push_on && pull_sp(lpw, epn, c)) {  // marks of last tick's push-write rows / this tick's
                         c.mark_cur = mark_tick == t - 1 ? d_mark[(t - 1) & 1] : nullptr;
                         mark_launches += c.mark_cur != nullptr;
@@ -3361,11 +3446,30 @@ int gossip_engine::decode_trace(int64_t t) {
             }
         }
     }
+    // folded rows (seen_fold): a tile written TM_FOLDW this tick holds seen | new -- the arrivals are the
+    // bits the node had not seen before the tick, which are in its row of the other F buffer (the tile
+    // was TM_SEENF this tick) or in its seen row (not written by a folding tick)
+    std::vector<uint64_t> Fp, Sp;
+    bool fold_f = false, fold_s = false;
+    for (uint32_t tl = 0; tl < tr_foldw.size(); tl++) {
+        fold_f |= tr_foldw[tl] && tr_seenf[tl];
+        fold_s |= tr_foldw[tl] && !tr_seenf[tl];
+    }
+    if (fold_f) {
+        Fp.resize((size_t)n * stride);
+        HIP_TRY(hipMemcpy(Fp.data(), d_F[fcur ^ 1], Fp.size() * 8, hipMemcpyDeviceToHost));
+    }
+    if (fold_s) {
+        Sp.resize((size_t)seen_n * stride);
+        HIP_TRY(hipMemcpy(Sp.data(), d_seen_mem, Sp.size() * 8, hipMemcpyDeviceToHost));
+    }
     for (uint32_t v = v0; v < v1; v++)
         for (uint32_t w = 0; w < hw; w++) {
             const uint32_t tl = w >> 4;
             if (!nz.empty() && !ws_tile[tl] && !((nz[(size_t)v * ntw + (tl >> 6)] >> (tl & 63u)) & 1ull)) continue;  // stale row
             uint64_t x = F[(size_t)v * stride + w];
+            if (tl < tr_foldw.size() && tr_foldw[tl])
+                x &= ~(tr_seenf[tl] ? Fp[(size_t)v * stride + w] : Sp[(size_t)(v - seen_lo) * stride + w]);
             while (x) {
                 const int b = __builtin_ctzll(x);
                 x &= x - 1;
@@ -3446,6 +3550,7 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
         e->opt_dense_rows = env_option("GOSSIP_DENSE_ROWS", -1);
         e->opt_peer_order = env_option("GOSSIP_PEER_ORDER", 1) != 0 ? 1 : 0;
         e->opt_pull_batch = env_option("GOSSIP_PULL_BATCH", 0) != 0 ? 1 : 0;
+        e->opt_seen_fold = std::max<int64_t>(-1, std::min<int64_t>(1, env_option("GOSSIP_SEEN_FOLD", -1)));
         e->trace = (cfg->flags & GOSSIP_F_TRACE) != 0;
         e->dense = cfg->mode == GOSSIP_MODE_DENSE;
         e->handshake = (cfg->flags & GOSSIP_F_HANDSHAKE) != 0;
@@ -3833,10 +3938,17 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
         e->opt_pull_tile_order = value;
     } else if (k == "pull_tiles") {
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "pull_tiles: 0 or 1");
+        if (value == 0 && e->any_folded())
+            return set_error(GOSSIP_EINVAL, "pull_tiles: a live tile was folded (seen_fold): the seen rows of its saturated nodes are stale and only the saturation bits of the tile lists' pull guard them");
         e->opt_pull_tiles = value;
     } else if (k == "pull_sat") {
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "pull_sat: 0 or 1");
+        if (value == 0 && e->any_folded())
+            return set_error(GOSSIP_EINVAL, "pull_sat: a live tile was folded (seen_fold): the seen rows of its saturated nodes are stale and only their saturation bits guard them");
         e->opt_pull_sat = value;
+    } else if (k == "seen_fold") {
+        if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "seen_fold: -1 (auto), 0 or 1");
+        e->opt_seen_fold = value;
     } else if (k == "dense_rows") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "dense_rows: -1 (auto), 0 or 1");
         e->opt_dense_rows = value;
@@ -3911,7 +4023,8 @@ int gossip_engine_get_option(const gossip_engine* e, const char* name, int64_t* 
         {"young_skip", e->opt_young_skip}, {"pull_push", e->opt_pull_push}, {"young_idle", e->opt_young_idle}, {"young_grid", e->opt_young_grid}, {"mem_limit", e->opt_mem_limit}, {"late_age", e->opt_late_age},
         {"xchunks", e->opt_xchunks}, {"rehearse_rows", e->opt_rehearse_rows},
         {"dense_fused", e->opt_dense_fused}, {"dense_min_tiles", e->opt_dense_min_tiles},
-        {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch}};
+        {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch},
+        {"seen_fold", e->opt_seen_fold}};
     for (const auto& o : opts)
         if (k == o.first) {
             *value = o.second;
@@ -4405,6 +4518,7 @@ int gossip_engine_get_counters(gossip_engine* e, gossip_counters* c) {
     c->pull_marks = acct[32];
     c->pull_sat = e->sat_used ? 1u : 0u;
     c->window_early_retires = e->early_retires;
+    c->pull_fold_rows = acct[33];
     uint64_t g = 0;
     const uint64_t done = (uint64_t)std::max<int64_t>(0, std::min(e->cur, e->tick_end) - e->tick0);
     if (!e->tick_lo.empty()) g = e->tick_lo[std::min<uint64_t>(done, e->tick_lo.size() - 1)];

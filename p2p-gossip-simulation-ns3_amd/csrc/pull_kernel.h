@@ -111,11 +111,14 @@ __device__ __forceinline__ uint32_t group_add(uint32_t x, uint32_t lane) {
 //        read it without occupancy words: dense rows, above)
 enum : uint32_t { WF_CLEAR = 1u, WF_GROUP = 2u, WF_KEEP = 4u, WF_SNAP = 8u, WF_YOUNG = 16u, WF_LATE = 32u,
                   WF_DW = 64u, WF_BIRTH = 128u };  // WF_BIRTH: a generation lands in the word this tick (k_dense_fused)
-// PullArgs::tmask, per occupancy word tw: [6 tw] dense-row tiles (read without occupancy words),
-// [6 tw + 1] tiles whose sat bits are trusted this tick, [6 tw + 2] listed tiles that need occupancy,
-// [6 tw + 3] push tiles (skipped at unmarked nodes), [6 tw + 4] push-write tiles (rows mark peers),
-// [6 tw + 5] exit-likely tiles (their passes gather short first batches, PULL_SHORT_B0 below)
-enum : uint32_t { TM_DENSE = 0, TM_SATOK = 1, TM_NZ = 2, TM_PUSH = 3, TM_PUSHW = 4, TM_SHORT = 5, TM_WORDS = 6 };
+// PullArgs::tmask, TM_WORDS words per occupancy word tw: [+0] dense-row tiles (read without occupancy
+// words), [+1] tiles whose sat bits are trusted this tick, [+2] listed tiles that need occupancy,
+// [+3] push tiles (skipped at unmarked nodes), [+4] push-write tiles (rows mark peers), [+5] exit-likely
+// tiles (their passes gather short first batches, PULL_SHORT_B0 below), [+6] folded-write tiles (the
+// F_next row carries seen | new, no seen write), [+7] tiles folded last tick (the own seen pair is read
+// from the node's F_cur row) -- option seen_fold, DESIGN section 3 "Folded rows"
+enum : uint32_t { TM_DENSE = 0, TM_SATOK = 1, TM_NZ = 2, TM_PUSH = 3, TM_PUSHW = 4, TM_SHORT = 5, TM_FOLDW = 6,
+                  TM_SEENF = 7, TM_WORDS = 8 };
 constexpr uint32_t kTmSlots = 16;  // LDS words for the launch's (<= 2) occupancy words of tmask
 
 constexpr uint32_t kPullLdsWords = 2048;  // words per launch: LDS liveness, new liveness, flags
@@ -209,10 +212,15 @@ __device__ __forceinline__ uint32_t pull_cid_load(const PullArgs& a, uint32_t st
 // SHORT (SP only): the batch schedule of exit-likely passes (tmask TM_SHORT, option pull_batch) -- its
 // own instantiation: the schedule's scalar state costs the item loop SGPR spills (65 -> 79), which
 // every launch without a flagged tile is spared
-template <int LPW, int EPN, bool NT = false, bool SP = false, bool PUSH = false, bool SHORT = false>
+// FOLD (SP only): folded rows (tmask TM_FOLDW / TM_SEENF, option seen_fold) -- launched only when some
+// tile of the launch carries a flag, so the plain instantiation keeps its registers; the kernels that
+// take sat bits at run time (EPN 1, not SP) always hold the code
+template <int LPW, int EPN, bool NT = false, bool SP = false, bool PUSH = false, bool SHORT = false, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1))) void k_pull(PullArgs a) {
     static_assert(SP || !PUSH, "push marks run in the SP instantiation");
     static_assert(SP || !SHORT, "the batch schedule runs in the SP instantiation");
+    static_assert(SP || !FOLD, "the SP launch picks the folding instantiation");
+    constexpr bool FOLDC = FOLD || (!SP && EPN == 1);
     const bool noskip = SP ? false : a.noskip != 0u;
     constexpr int GRP = LPW * EPN;  // lanes per node
     constexpr int NPW = 64 / GRP;   // nodes per wave step
@@ -348,6 +356,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
     uint32_t t_pe = 0, t_col = 0, t_srd = 0, t_swr = 0, t_fwr = 0, t_nz = 0, t_sk = 0;  // wave-uniform
     uint32_t t_it = 0, t_gi = 0;  // node items, node items that gathered
     uint32_t t_mk = 0;            // push marks set (one 8-B atomic each)
+    uint32_t t_fold = 0;          // tile rows written folded
     unsigned long long nzacc = 0ull;
     const bool gather = EPN == 1;  // the pipelined id/occupancy loads
     const uint32_t tw_base = a.wbase >> 10;  // the launch's first occupancy word
@@ -360,6 +369,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
     // dense-row nor saturated at the node)?
     auto nz_needed = [&](uint32_t idx, uint32_t tw) -> bool {
         return !tm_on || (s_tm[(tw - tw_base) * TM_WORDS + TM_NZ] & ~satv_of(idx, tw)) != 0ull;
+    };
+
+    // Folded rows: is the tile of global word wg (occupancy word tw) flagged in tmask word `which`?
+    auto tm_bit = [&](uint32_t which, uint32_t tw, uint32_t wg) -> bool {
+        if constexpr (!FOLDC) return false;
+        return sat_on && ((s_tm[(tw - tw_base) * TM_WORDS + which] >> ((wg >> 4) & 63u)) & 1ull) != 0ull;
     };
 
     for (uint64_t c0 = a.v0 + wave * 64u; npass && c0 < n; c0 += nwaves * 64u) {
@@ -440,7 +455,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
             const uint32_t lw = lw_of(pass, wl);
             if (v < n && lw != kNoWord && (s_lp[lw] | s_lp[lw + 1u]) != 0ull &&
                 !((satv_of(step * NPW + slot, tw_of(pass)) >> (((a.wbase + lw) >> 4) & 63u)) & 1ull))
-                s2c = load_row16<NT>(a.seen + v * stride + a.wbase + lw);
+                // (a tile folded last tick: the seen pair is in the node's own F_cur row)
+                s2c = load_row16<NT>((tm_bit(TM_SEENF, tw_of(pass), a.wbase + lw) ? a.Fcur : a.seen) + v * stride + a.wbase + lw);
         }
         uint32_t cid0 = 0xffffffffu, cid1 = 0xffffffffu;
         unsigned long long nz0 = 0ull;
@@ -511,11 +527,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
                 const int32_t b0 = beg, e0 = end;  // (this item's node)
                 if (v1 < n && lw1 != kNoWord && (s_lp[lw1] | s_lp[lw1 + 1u]) != 0ull) {
                     // same node and occupancy word as this item, peers in one lane group
-                    s2n_gated = gate && step1 == step && tw_of(pass1) == tw && e0 - b0 <= GRP &&
+                    // (never a tile whose seen pair is in its F_cur row: the exit tick stores it)
+                    const bool sf1 = tm_bit(TM_SEENF, tw_of(pass1), a.wbase + lw1);
+                    s2n_gated = gate && step1 == step && tw_of(pass1) == tw && e0 - b0 <= GRP && !sf1 &&
                                 !((nzor >> (((a.wbase + lw1) >> 4) & 63u)) & 1ull);
                     // a saturated tile (trusted sat bit) needs nothing: not even its seen words
                     s2n_gated |= ((satv_of(step1 * NPW + slot, tw_of(pass1)) >> (((a.wbase + lw1) >> 4) & 63u)) & 1ull) != 0ull;
-                    if (!s2n_gated) s2n = load_row16<NT>(a.seen + v1 * stride + a.wbase + lw1);
+                    if (!s2n_gated) s2n = load_row16<NT>((sf1 ? a.Fcur : a.seen) + v1 * stride + a.wbase + lw1);
                 }
             }
             uint32_t cid2 = 0xffffffffu;
@@ -711,8 +729,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
             // keep-masked word's dropped columns are unseen too: never saturated on a keep tick)
             // The bit is updated in place in the node's LDS sat word, which the occupancy word's
             // last item writes back whole.
+            int un = 0;  // the tile still has a live column this node has not seen
             if (sat_on) {
-                int un = ((want0 & ~n0) | (want1 & ~n1)) != 0ull || ((f0 | f1) & WF_KEEP) != 0u;
+                un = ((want0 & ~n0) | (want1 & ~n1)) != 0ull || ((f0 | f1) & WF_KEEP) != 0u;
                 un = (int)group_or<8>((uint32_t)un, lane);
                 if (act && (wl & 7u) == 0u) {
                     unsigned long long* sw = s_satw + idx * 2u + (tw - tw_base);
@@ -724,15 +743,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
             }
             // ---- state, counters (one lane per word pair) ----
             const bool own = act && el == 0;
-            const bool swr = own && (dead ? ((f0 | f1) & WF_CLEAR) != 0u
-                                          : ((n0 | n1) != 0ull || ((f0 | f1) & WF_CLEAR) != 0u));
+            // Folded rows (header comment of engine.hip step 4c).  fw: the F_next row
+            // carries seen | new and the seen row is not written (a dead or saturated pair stores
+            // zeros: never read back).  ex: the tile was folded last tick and is not this tick -- a
+            // node it still is unsaturated at stores its seen pair once (s2 came from its F_cur
+            // row), a saturated one never reads it again.
+            const bool fw = tm_bit(TM_FOLDW, tw, w), ex = !fw && tm_bit(TM_SEENF, tw, w);
+            const bool swr = own && !fw &&
+                             (ex ? !dead && un != 0
+                                 : dead ? ((f0 | f1) & WF_CLEAR) != 0u
+                                        : ((n0 | n1) != 0ull || ((f0 | f1) & WF_CLEAR) != 0u));
+            const bool fo = fw && !dead;
+            t_fold += wave_count(own && trow && fw && (wl & 7u) == 0u);
             t_fwr += wave_count(own && trow);
             t_srd += wave_count(own && !dead && !s2c_gated);
             t_swr += wave_count(swr);
             if (own) {
                 uint64_t* sp = a.seen + (uint64_t)v * stride + w;
                 uint64_t* fp = a.Fnext + (uint64_t)v * stride + w;
-                if (trow) store_row16<NT>(fp, n0, n1);
+                if (trow) store_row16<NT>(fp, fo ? s2.x | n0 : n0, fo ? s2.y | n1 : n1);
                 if (swr) {
                     if (dead && !((f0 & f1) & WF_CLEAR))
                         sp[(f0 & WF_CLEAR) ? 0 : 1] = 0ull;
@@ -813,10 +842,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 5 : 1)
         if (lane_id == 0 && snap_local) atomicAdd(a.snap, snap_local);
     }
     if (a.acct && lane_id == 0) {
-        const uint32_t tv[10] = {t_pe, t_col, t_srd, t_swr, t_fwr, t_nz, t_sk, t_it, t_gi, t_mk};
-        const int slot_of[10] = {0, 1, 2, 3, 4, 7, 16, 20, 21, 32};
+        const uint32_t tv[11] = {t_pe, t_col, t_srd, t_swr, t_fwr, t_nz, t_sk, t_it, t_gi, t_mk, t_fold};
+        const int slot_of[11] = {0, 1, 2, 3, 4, 7, 16, 20, 21, 32, 33};
 #pragma unroll
-        for (int q = 0; q < 10; q++)
+        for (int q = 0; q < 11; q++)
             if (tv[q]) acct_add(a.acct, (uint32_t)slot_of[q], (unsigned long long)tv[q]);
     }
     __syncthreads();

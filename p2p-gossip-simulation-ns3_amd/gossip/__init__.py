@@ -117,7 +117,7 @@ class gossip_counters(C.Structure):
         ("dense_fused_launches", C.c_uint64),
         ("young_grid", C.c_uint32), ("young_skip_ticks", C.c_uint32),
         ("pull_push_tiles", C.c_uint64), ("pull_pushw_tiles", C.c_uint64), ("pull_marks", C.c_uint64),
-        ("young_idle_ticks", C.c_uint64),
+        ("young_idle_ticks", C.c_uint64), ("pull_fold_rows", C.c_uint64),
     ]
 
 
