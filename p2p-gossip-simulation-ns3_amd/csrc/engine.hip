@@ -47,8 +47,13 @@
 #include <vector>
 
 #include "internal.h"
+#include "pull_plan.h"
 
 using gossip::set_error;
+using gossip::PullShape;
+using gossip::PullWindow;
+using gossip::TickPlan;
+using gossip::pull_shape;
 
 namespace {
 
@@ -125,10 +130,11 @@ struct PullArgs {
     uint32_t shared_out = 0;
     uint32_t keep_lds = 0;  // some word of the launch has WF_KEEP: masks staged in LDS (k_pull)
     uint32_t gate_seen = 1;  // k_pull<LPW,1>: skip the own-seen loads of tiles no peer occupies
-    // Pass -> tile map (option pull_tiles): a k_pull pass covers LPW / 8 tiles taken from this
-    // list of launch-local tile indices (0xffff = padding) instead of LPW / 8 consecutive tiles,
-    // so passes skip tiles that hold nothing for k_pull (young, retired); every group of LPW / 8
-    // entries lies in one occupancy word.  Null: consecutive tiles.
+    // Pass -> tile map (option pull_tiles): a k_pull pass covers the launch shape's tiles_per_pass
+    // (pull_plan.h) tiles taken from this list of launch-local tile indices (0xffff = padding)
+    // instead of as many consecutive tiles, so passes skip tiles that hold nothing for k_pull
+    // (young, retired); every group of tiles_per_pass entries lies in one occupancy word.  Null:
+    // consecutive tiles.
     const uint16_t* ptile = nullptr;
     uint32_t nptile = 0;
     // Saturated tiles and dense-row tiles (k_pull<LPW,1> over tile lists; pull_kernel.h): per node
@@ -250,15 +256,13 @@ uint64_t pull_grid_cap(bool nt, int64_t ov) {
     return nt ? 16384ull : 4096ull;
 }
 
-// Word-lanes per node of the sparse pull for windows wider than 64 words: 32 (passes of 64 words,
-// two nodes per wave step: twice the independent peer chains per wave, and a window never ends in
-// a half-idle 128-word pass).  Measured against 64 lanes (profiles/r01/lanes_ab.json: C4 1216
-// words 127.7 -> 121.9 ms per launch, the 8-shard 320 words 44.0 -> 36.5 ms, C3 3.35 -> 3.06 ms),
-// 16 lanes (C4 128.0 ms) and again in round 4 (64 lanes: C4 phase 69.0 vs 60.4 ms,
-// profiles/r04/ab/r4l_*); the option that selected them was removed in round 5.
-constexpr int kWideLanes = 32;
+// the flags k_pull<.., SP = true> takes as compile-time constants (pull_kernel.h): the same
+// conditions the kernel derives at run time.  Push marks (PullArgs::mark_*) run only there.
+bool pull_sp(int lpw, int epn, const PullArgs& a) {
+    return lpw == 32 && epn == 1 && a.tmask != nullptr && a.ptile != nullptr && a.sat != nullptr &&
+           a.nptile / (uint32_t)(lpw / 8) <= kPullMaxPasses && !a.noskip && a.gate_seen;
+}
 
-bool pull_sp(int lpw, int epn, const PullArgs& a);
 // the SP instantiations: push marks, the batch schedule of exit-likely passes and folded rows each in
 // instantiations of their own (the plain one keeps its register allocation)
 template <int LPW, bool SHORT, bool FOLD>
@@ -288,20 +292,13 @@ void launch_pull_t(bool nt, uint32_t grid, size_t lds, hipStream_t s, const Pull
             return;
         }
     }
-    if constexpr ((LPW == 64 || LPW == 32 || LPW == 16) && EPN == 1) {
+    if constexpr ((LPW == 32 || LPW == 16) && EPN == 1) {
         if (nt) {
             k_pull<LPW, 1, true><<<grid, 256, lds, s>>>(a);
             return;
         }
     }
     if constexpr (LPW * EPN <= 64) k_pull<LPW, EPN><<<grid, 256, lds, s>>>(a);
-}
-
-// the flags k_pull<.., SP = true> takes as compile-time constants (pull_kernel.h): the same
-// conditions the kernel derives at run time.  Push marks (PullArgs::mark_*) run only there.
-bool pull_sp(int lpw, int epn, const PullArgs& a) {
-    return lpw == 32 && epn == 1 && a.tmask != nullptr && a.ptile != nullptr && a.sat != nullptr &&
-           a.nptile / (uint32_t)(lpw / 8) <= kPullMaxPasses && !a.noskip && a.gate_seen;
 }
 
 template <int LPW>
@@ -315,13 +312,14 @@ void launch_pull_e(int epn, bool nt, uint32_t grid, size_t lds, hipStream_t s, c
     }
 }
 
-// (LPW, EPN) with 8 <= LPW, LPW * EPN <= 64, both powers of two.
-void launch_pull(int lpw, int epn, bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
-    switch (lpw) {  // lpw >= 8: one tile's 8 word-pairs sit in one lane group
-        case 8: launch_pull_e<8>(epn, nt, grid, lds, s, a); break;
-        case 16: launch_pull_e<16>(epn, nt, grid, lds, s, a); break;
-        case 32: launch_pull_e<32>(epn, nt, grid, lds, s, a); break;
-        default: launch_pull_e<64>(epn, nt, grid, lds, s, a); break;
+// The k_pull instantiation of a launch shape (pull_plan.h: lpw 8, 16 or 32, lpw * epn <= 64, both
+// powers of two).  False: no instantiation takes that lpw, nothing was launched.
+bool launch_pull(const PullShape& sh, bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    switch (sh.lpw) {  // lpw >= 8: one tile's 8 word-pairs sit in one lane group
+        case 8: launch_pull_e<8>(sh.epn, nt, grid, lds, s, a); return true;
+        case 16: launch_pull_e<16>(sh.epn, nt, grid, lds, s, a); return true;
+        case 32: launch_pull_e<32>(sh.epn, nt, grid, lds, s, a); return true;
+        default: return false;
     }
 }
 
@@ -846,7 +844,6 @@ struct gossip_engine {
     uint16_t* h_ptile[kRing] = {};
     uint16_t* d_ptile[kRing] = {};
     uint64_t ptile_cap = 0;
-    std::vector<uint32_t> pt_off, pt_cnt;  // per launch window of this tick
     bool pt_used = false;                  // the last tick's k_pull ran over tile lists
     // Saturated tiles and dense-row tiles (pull_kernel.h; options pull_sat, dense_rows)
     int64_t opt_pull_sat = 1;              // 1: k_pull keeps and trusts per-node saturation bits
@@ -869,7 +866,6 @@ struct gossip_engine {
     std::vector<int64_t> tile_foldw;       // last tick k_pull wrote the tile's rows folded (TM_FOLDW)
     std::vector<uint8_t> tile_folded;      // the tile was folded in this life: saturated nodes' seen rows are stale
     bool fold_barred = false;              // a tick dropped receptions by a keep mask: peers' old bits are no longer safe
-    std::vector<uint8_t> fold_launch;      // per launch window of this tick: some tile carries TM_FOLDW / TM_SEENF
     std::vector<uint8_t> tr_foldw, tr_seenf;  // per tile: this tick's TM_FOLDW / TM_SEENF (decode_trace)
     bool any_folded() const {
         for (size_t tl = 0; tl < tile_folded.size() && tl < tile_alloc.size(); tl++)
@@ -1025,6 +1021,26 @@ struct gossip_engine {
     int64_t packed_tick = -1;        // host-staged export: message of (tick, chunk) already packed
     uint32_t packed_chunk = 0;
     void chunk_rows(uint32_t r, uint32_t c, uint64_t* lo, uint64_t* hi) const;
+    TickPlan plan;  // this tick's (pull_plan.h): reset by tick_step_a, filled by its stages
+    // tick_step_a's stages, in order; each fills its part of the tick's plan (TickPlan)
+    int stage_births(TickPlan& p);
+    int plan_young(TickPlan& p);
+    void group_births_by_chunk(TickPlan& p);
+    void build_word_ctl(TickPlan& p);
+    int build_tile_lists(TickPlan& p);
+    int build_tile_masks(TickPlan& p);
+    int launch_tick(TickPlan& p);
+    // launch_tick's launches
+    uint32_t young_cap() const {  // slot entries per node (option young_cap) that fit a slot
+        return (uint32_t)std::min<int64_t>(kSlotU16 - 1, std::max<int64_t>(1, opt_young_cap));
+    }
+    uint32_t grid_for(const TickPlan& p, uint64_t lo, uint64_t hi) const;
+    int launch_births(const TickPlan& p, uint32_t off, uint32_t cnt);
+    int end_chunk(uint32_t c);
+    int run_pull(const TickPlan& p, const PullArgs& base);
+    int launch_young(const TickPlan& p, const PullArgs& a, hipStream_t ys);
+    void run_dedup(const PullArgs& base);
+    int run_dense(uint64_t lo, uint64_t hi, const unsigned long long* live_prev);
     int pack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, hipStream_t s);
     int unpack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, const uint64_t* msg, uint64_t words,
                      hipStream_t s);
@@ -1891,7 +1907,20 @@ int gossip_engine::tick_step(int64_t t) {
 }
 
 int gossip_engine::tick_step_a(int64_t t) {
-    const int slot = (int)(t % kRing);
+    TickPlan& p = plan;
+    p.reset(t, (int)(t % kRing));
+    int rc;
+    if ((rc = stage_births(p))) return rc;
+    if ((rc = plan_young(p))) return rc;
+    group_births_by_chunk(p);
+    build_word_ctl(p);
+    if ((rc = build_tile_lists(p))) return rc;
+    if ((rc = build_tile_masks(p))) return rc;
+    return launch_tick(p);
+}
+
+int gossip_engine::stage_births(TickPlan& p) {
+    const int64_t t = p.t;
     // 1. liveness of tick t-kLag -> retire words whose floods have drained.
     {
         const int64_t kt = t - kLag;
@@ -1904,15 +1933,14 @@ int gossip_engine::tick_step_a(int64_t t) {
         }
     }
     // 2. staging slot reuse
-    HIP_TRY(hipEventSynchronize(slot_done[slot]));
+    HIP_TRY(hipEventSynchronize(slot_done[p.slot]));
     // 3. births of tick t
     reset_now.clear();
-    uint32_t nb = 0, np = 0;
     // (hop-batched runs keep stepping after the last birth tick until the floods retire)
     const size_t tb = (size_t)(t - tick0);
     const uint64_t lo = tb + 1 < tick_lo.size() ? tick_lo[tb] : 0, hi = tb + 1 < tick_lo.size() ? tick_lo[tb + 1] : 0;
-    Birth* B = h_births[slot];
-    int32_t* GP = h_gphase[slot];
+    Birth* B = h_births[p.slot];
+    int32_t* GP = h_gphase[p.slot];
     for (uint64_t q = lo; q < hi; q++) {
         const gossip_gen_event& e = ev[q];
         Instance& I = inst[ev_inst[q]];
@@ -1967,22 +1995,25 @@ int gossip_engine::tick_step_a(int64_t t) {
                 b.kind = BIRTH_GROUP;
                 b.glo = I.lo;
                 b.glen = I.nsrc;
-                b.poff = np;
+                b.poff = p.np;
                 for (uint32_t r = 0; r < I.nsrc; r++)
-                    GP[np++] = col_phase[(size_t)I.word * 64 + I.lo + r];
+                    GP[p.np++] = col_phase[(size_t)I.word * 64 + I.lo + r];
             } else {
                 b.kind = BIRTH_NORMAL;
             }
         }
-        if (e.node >= v0 && e.node < v1) B[nb++] = b;  // row partition: own nodes only
+        if (e.node >= v0 && e.node < v1) B[p.nb++] = b;  // row partition: own nodes only
     }
+    return GOSSIP_OK;
+}
+
+int gossip_engine::plan_young(TickPlan& p) {
+    const int64_t t = p.t;
+    Birth* B = h_births[p.slot];
     // 3b. young tiles of this tick (young_kernel.h): every tile F_cur holds in slots (it was
     //     write-sparse last tick) plus fresh tiles opened by this tick's births; the youngest of
     //     them stay (or become) write-sparse while their oldest shares are <= young_age hops old.
-    uint32_t ny = 0, nwt = 0, ny_read = 0, ny_leave = 0;
-    bool skip_wr = false;  // this tick's slot writers stamp non-empty slots (young_skip)
-    YoungPack* YP = young ? h_young[slot] : nullptr;
-    std::vector<uint8_t> new_widx;
+    YoungPack* YP = young ? h_young[p.slot] : nullptr;
     if (young) {
         const uint32_t ntiles = hw / kTileWords;
         struct Cand {
@@ -2002,15 +2033,15 @@ int gossip_engine::tick_step_a(int64_t t) {
         std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) {
             return a.first != b.first ? a.first > b.first : a.tile < b.tile;  // youngest first
         });
-        new_widx.assign(tile_widx.size(), 0xffu);
+        p.new_widx.assign(tile_widx.size(), 0xffu);
         // read tiles sit at their F_cur entry index (young_kernel.h): nr = last tick's write count
-        ny_read = (uint32_t)wt_last.size();
-        for (uint32_t r = 0; r < ny_read; r++) YP->yt[r] = YoungTile{wt_last[r], 0u, (uint8_t)r, 0xffu, 0};
+        p.ny_read = (uint32_t)wt_last.size();
+        for (uint32_t r = 0; r < p.ny_read; r++) YP->yt[r] = YoungTile{wt_last[r], 0u, (uint8_t)r, 0xffu, 0};
         uint32_t nfresh = 0;
         YoungTile fresh[kYoungMax];
         uint32_t fresh_room = kYoungMax > nrd ? kYoungMax - nrd : 0u;  // nrd <= kYoungWriteMax < kYoungMax
         for (const Cand& c : cand) {
-            const bool wr_age = t + 1 - c.first <= opt_young_age && nwt < kYoungWriteMax;
+            const bool wr_age = t + 1 - c.first <= opt_young_age && p.nwt < kYoungWriteMax;
             if (!c.rd) {
                 if (!wr_age || fresh_room == 0) continue;  // stays a dense tile (it is dead this tick)
                 fresh_room--;
@@ -2018,9 +2049,9 @@ int gossip_engine::tick_step_a(int64_t t) {
             YoungTile y{c.tile, (uint8_t)((c.rd ? YT_READ : 0u) | (wr_age ? YT_WRITE : 0u)),
                         c.rd ? tile_widx[c.tile] : (uint8_t)0xffu, (uint8_t)0xffu, 0};
             if (wr_age) {
-                y.w_idx = (uint8_t)nwt;
-                YP->wt[nwt++] = c.tile;
-                new_widx[c.tile] = y.w_idx;
+                y.w_idx = (uint8_t)p.nwt;
+                YP->wt[p.nwt++] = c.tile;
+                p.new_widx[c.tile] = y.w_idx;
             }
             if (c.rd)
                 YP->yt[y.r_idx] = y;  // (a read tile whose tile is gone keeps flags 0: no output)
@@ -2028,18 +2059,18 @@ int gossip_engine::tick_step_a(int64_t t) {
                 fresh[nfresh++] = y;
         }
         std::sort(fresh, fresh + nfresh, [](const YoungTile& a, const YoungTile& b) { return a.tile < b.tile; });
-        for (uint32_t k = 0; k < nfresh; k++) YP->yt[ny_read + k] = fresh[k];
-        ny = ny_read + nfresh;
-        for (uint32_t r = 0; r < ny_read; r++)
-            if (YP->yt[r].flags == YT_READ) YP->lv[ny_leave++] = (uint8_t)r;
-        std::sort(YP->lv, YP->lv + ny_leave, [&](uint8_t a, uint8_t b) { return YP->yt[a].tile < YP->yt[b].tile; });
+        for (uint32_t k = 0; k < nfresh; k++) YP->yt[p.ny_read + k] = fresh[k];
+        p.ny = p.ny_read + nfresh;
+        for (uint32_t r = 0; r < p.ny_read; r++)
+            if (YP->yt[r].flags == YT_READ) YP->lv[p.ny_leave++] = (uint8_t)r;
+        std::sort(YP->lv, YP->lv + p.ny_leave, [&](uint8_t a, uint8_t b) { return YP->yt[a].tile < YP->yt[b].tile; });
         // young ids (the seen lists' tile index, young_kernel.h): a fresh young tile takes the lowest
         // free id; a tile leaving the set (or gone) gives its id back after this tick -- this
         // tick's k_pull_young drops its entries from every list, so no list still names it
         std::memset(YP->ymap, 0xff, sizeof(YP->ymap));
         std::memset(YP->wt_yid, 0xff, sizeof(YP->wt_yid));
         uint64_t yid_free_after = 0;
-        for (uint32_t q = 0; q < ny; q++) {
+        for (uint32_t q = 0; q < p.ny; q++) {
             YoungTile& y = YP->yt[q];
             uint8_t id = tile_yid[y.tile];
             if (id == kYidNone) {  // a fresh tile
@@ -2054,34 +2085,41 @@ int gossip_engine::tick_step_a(int64_t t) {
             if (y.flags & YT_WRITE) YP->wt_yid[y.w_idx] = id;
             else yid_free_after |= 1ull << id;  // leaving, or its tile is gone
         }
-        for (uint32_t q = 0; q < ny; q++)
+        for (uint32_t q = 0; q < p.ny; q++)
             if ((yid_free_after >> YP->yt[q].yid) & 1ull) tile_yid[YP->yt[q].tile] = kYidNone;
         yid_used &= ~yid_free_after;
-        for (uint32_t q = 0; q < nb; q++) {
+        for (uint32_t q = 0; q < p.nb; q++) {
             const uint32_t tl = B[q].col >> 10;
-            B[q].widx = tl < new_widx.size() ? new_widx[tl] : 0xffu;
+            B[q].widx = tl < p.new_widx.size() ? p.new_widx[tl] : 0xffu;
             B[q].yid = B[q].widx != 0xffu ? tile_yid[tl] : kYidNone;
         }
         // empty-slot skipping: expected slot entries per node of F_next = sum over the write-sparse
         // tiles of columns x frontier fraction at F_next's hop (t - first: births are hop 0), and a
         // node's slot is non-empty with probability 1 - e^-entries
-        skip_wr = false;
+        p.skip_wr = false;
         if (opt_young_skip == 1) {
-            skip_wr = nwt > 0;
-        } else if (opt_young_skip == -1 && nwt) {
+            p.skip_wr = p.nwt > 0;
+        } else if (opt_young_skip == -1 && p.nwt) {
             double e = 0.0;
-            for (uint32_t q = 0; q < nwt; q++) e += frontier_entries(YP->wt[q], t);
-            skip_wr = 1.0 - std::exp(-e) < kSkipSlotFrac;
+            for (uint32_t q = 0; q < p.nwt; q++) e += frontier_entries(YP->wt[q], t);
+            p.skip_wr = 1.0 - std::exp(-e) < kSkipSlotFrac;
         }
     } else {
-        for (uint32_t q = 0; q < nb; q++) B[q].widx = 0xffu;
+        for (uint32_t q = 0; q < p.nb; q++) B[q].widx = 0xffu;
     }
+    return GOSSIP_OK;
+}
+
+void gossip_engine::group_births_by_chunk(TickPlan& p) {
+    Birth* B = h_births[p.slot];
+    const uint32_t nb = p.nb;
     // 3c. row chunks of the pipelined exchange: births grouped by chunk (a node has at most one
     //     birth per tick, so their order inside a launch is free)
     fused_rows = row_count > 1 && dense && opt_dense_fused && (comm || group_mode) && max_group_phases == 0 &&
                  !(cfg.flags & GOSSIP_F_NOSKIP);
     nchunks = (row_count > 1 && !fused_rows) ? (uint32_t)std::min<int64_t>(kMaxChunks, std::max<int64_t>(1, opt_xchunks)) : 1u;
-    uint32_t cb_off[kMaxChunks + 1] = {};
+    std::vector<uint32_t>& cb_off = p.cb_off;
+    cb_off.assign(kMaxChunks + 1, 0u);
     cb_off[1] = nb;
     if (nchunks > 1) {
         uint64_t clo[kMaxChunks + 1];
@@ -2096,22 +2134,24 @@ int gossip_engine::tick_step_a(int64_t t) {
         for (uint32_t c = 0; c < nchunks; c++) cb_off[c + 1] = cb_off[c] + cnt[c];
         std::vector<Birth> tmp(B, B + nb);
         uint32_t at[kMaxChunks];
-        std::copy(cb_off, cb_off + nchunks, at);
+        std::copy(cb_off.begin(), cb_off.begin() + nchunks, at);
         for (uint32_t q = 0; q < nb; q++) B[at[chunk_of(tmp[q].node)]++] = tmp[q];
     }
+}
+
+void gossip_engine::build_word_ctl(TickPlan& p) {
+    const int64_t t = p.t;
     // 4. per-word control for this tick
     for (uint32_t w : reset_now) ctl[w].clear = ~0ull;
     const bool is_cut = (t == cut_tick && cut_r > 0);
-    int snap_idx = -1;
     for (size_t s = 0; s < snaps.size() && !batch; s++)
-        if (snaps[s].tick == t && snaps[s].r > 0) snap_idx = (int)s;
-    WordCtl* C = h_ctl[slot];
-    uint8_t* WF = h_wflags[slot];
-    const size_t nsnap = batch ? snaps.size() : 0;
-    bool smask_any = false;
-    if (nsnap && hw) std::memset(h_smask[slot], 0, (size_t)nsnap * hw * 8);
-    bool keep_any = false;  // some word has a keep mask (k_pull stages them in LDS)
-    bool group_any = false; // some word holds an id group (k_dense_fused leaves those ticks to the 3-kernel path)
+        if (snaps[s].tick == t && snaps[s].r > 0) p.snap_idx = (int)s;
+    const int snap_idx = p.snap_idx;
+    WordCtl* C = h_ctl[p.slot];
+    uint8_t* WF = h_wflags[p.slot];
+    p.nsnap = batch ? snaps.size() : 0;
+    const size_t nsnap = p.nsnap;
+    if (nsnap && hw) std::memset(h_smask[p.slot], 0, (size_t)nsnap * hw * 8);
     for (uint32_t w = 0; w < hw; w++) {
         WordCtl c = ctl[w];
         if (batch) {
@@ -2130,8 +2170,8 @@ int gossip_engine::tick_step_a(int64_t t) {
                 if (ta < cfg.t_cut_ns) km |= 1ull << bb;
                 for (size_t s = 0; s < nsnap; s++)
                     if (hop >= 1 && ta < snaps[s].t_ns) {
-                        h_smask[slot][s * hw + w] |= 1ull << bb;
-                        smask_any = true;
+                        h_smask[p.slot][s * hw + w] |= 1ull << bb;
+                        p.smask_any = true;
                     }
             }
             c.keep = km;
@@ -2148,31 +2188,41 @@ int gossip_engine::tick_step_a(int64_t t) {
         C[w] = c;
         WF[w] = (uint8_t)((c.clear ? WF_CLEAR : 0u) | (c.gmask ? WF_GROUP : 0u) |
                           (c.keep != ~0ull ? WF_KEEP : 0u) | (c.snap ? WF_SNAP : 0u));
-        keep_any |= c.keep != ~0ull;
-        group_any |= c.gmask != 0ull;
+        p.keep_any |= c.keep != ~0ull;
+        p.group_any |= c.gmask != 0ull;
     }
     if (const int64_t late = late_age_now())  // bottom-up early exit in k_pull (tiles >= late ticks old)
         for (uint32_t w = 0; w < hw; w++) {
             const uint32_t tl = w / kTileWords;
             if (tile_alloc[tl] && t + 1 - tile_first[tl] >= late) WF[w] |= (uint8_t)WF_LATE;
         }
-    for (uint32_t i = 0; i < ny; i++)  // k_pull leaves these words to k_pull_young
+    const YoungPack* YP = h_young[p.slot];
+    for (uint32_t i = 0; i < p.ny; i++)  // k_pull leaves these words to k_pull_young
         if (YP->yt[i].flags)
             for (uint32_t q = 0; q < kTileWords; q++) WF[YP->yt[i].tile * kTileWords + q] |= (uint8_t)WF_YOUNG;
     for (uint32_t w : reset_now) ctl[w].clear = 0ull;
-    for (uint32_t q = 0; q < nb; q++)  // (k_dense_fused writes the 16-word tiles births land in)
+    const Birth* B = h_births[p.slot];
+    for (uint32_t q = 0; q < p.nb; q++)  // (k_dense_fused writes the 16-word tiles births land in)
         if (B[q].kind == BIRTH_NORMAL || B[q].kind == BIRTH_GROUP) WF[B[q].col >> 6] |= (uint8_t)WF_BIRTH;
+}
+
+int gossip_engine::build_tile_lists(TickPlan& p) {
+    [[maybe_unused]] const int64_t t = p.t;  // (PULL_DIAG_SKIP)
+    const uint8_t* WF = h_wflags[p.slot];
     // 4b. k_pull's pass -> tile lists (option pull_tiles), one per launch window: the allocated,
-    //     non-young tiles, grouped by occupancy word and padded to whole passes of LPW / 8 tiles
-    //     (LPW as run_pull picks it below).  Young tiles are k_pull_young's, retired tiles hold
-    //     nothing; a pass then never spends its lanes on them.
-    pt_off.clear();
-    pt_cnt.clear();
-    const bool use_ptile = opt_pull_tiles && !dense && !(cfg.flags & GOSSIP_F_NOSKIP) && hw;
-    pt_used = use_ptile;
-    const bool sat_on = use_ptile && opt_pull_sat != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP) && d_sat;
-    const bool dr_used = use_ptile && opt_dense_rows != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP);
-    if (use_ptile) {
+    //     non-young tiles, grouped by occupancy word and padded to whole passes of the window's
+    //     shape (pull_plan.h).  Young tiles are k_pull_young's, retired tiles hold nothing; a pass
+    //     then never spends its lanes on them.
+    const double avg_deg = n ? (double)nnz / n : 0.0;
+    for (uint32_t wb = 0; wb < hw; wb += kPullLdsWords) {
+        const uint32_t wl = std::min(kPullLdsWords, hw - wb);
+        p.windows.push_back(PullWindow{wb, wl, pull_shape(wl, avg_deg), 0u, 0u, false});
+    }
+    p.use_ptile = opt_pull_tiles && !dense && !(cfg.flags & GOSSIP_F_NOSKIP) && hw;
+    pt_used = p.use_ptile;
+    p.sat_used = p.use_ptile && opt_pull_sat != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP) && d_sat;
+    p.dr_used = p.use_ptile && opt_dense_rows != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP);
+    if (p.use_ptile) {
         const uint64_t need = (uint64_t)hw / kTileWords + 16ull * ((hw + kPullLdsWords - 1) / kPullLdsWords) + 16;
         if (need > ptile_cap) {
             HIP_TRY(hipStreamSynchronize(stream));
@@ -2184,16 +2234,12 @@ int gossip_engine::tick_step_a(int64_t t) {
             }
             ptile_cap = need;
         }
-        uint16_t* P = h_ptile[slot];
+        uint16_t* P = h_ptile[p.slot];
         uint32_t at = 0;
-        for (uint32_t wb = 0; wb < hw; wb += kPullLdsWords) {
-            const uint32_t wl = std::min(kPullLdsWords, hw - wb);
-            int lpw = 8;
-            while (lpw < 64 && 2 * lpw < (int)wl) lpw *= 2;
-            if (lpw == 64) lpw = kWideLanes;  // (run_pull: wide windows)
-            const uint32_t tpp = (uint32_t)lpw / 8u;
-            pt_off.push_back(at);
-            const uint32_t t0 = wb / kTileWords, t1 = (wb + wl) / kTileWords;
+        for (PullWindow& win : p.windows) {
+            const uint32_t tpp = win.shape.tiles_per_pass();
+            win.pt_off = at;
+            const uint32_t t0 = win.wb / kTileWords, t1 = (win.wb + win.words) / kTileWords;
             // per occupancy word, the tiles in age order (option pull_tile_order): a pass's tiles
             // then reach their early exit (late_age) after similar numbers of peer batches, so
             // fewer lanes idle while the wave finishes the pass's slowest tile
@@ -2216,10 +2262,17 @@ int gossip_engine::tick_step_a(int64_t t) {
                 grp.push_back(tl);
             }
             flush();
-            pt_cnt.push_back(at - pt_off.back());
+            win.pt_cnt = at - win.pt_off;
         }
-        if (at) HIP_TRY(hipMemcpyAsync(d_ptile[slot], P, (size_t)at * 2, hipMemcpyHostToDevice, stream));
+        if (at) HIP_TRY(hipMemcpyAsync(d_ptile[p.slot], P, (size_t)at * 2, hipMemcpyHostToDevice, stream));
     }
+    return GOSSIP_OK;
+}
+
+int gossip_engine::build_tile_masks(TickPlan& p) {
+    const int64_t t = p.t;
+    uint8_t* WF = h_wflags[p.slot];
+    YoungPack* YP = h_young[p.slot];
     // 4c. saturation bits and dense-row tiles of k_pull (pull_kernel.h), per listed tile:
     //   dense row (TM_DENSE): every node's F_cur row of the tile was written last tick (WF_DW by
     //     k_pull, YT_DW by k_pull_young for a tile leaving the young set) -- read without
@@ -2230,36 +2283,23 @@ int gossip_engine::tick_step_a(int64_t t) {
     //     and no birth landed in it since then (a birth adds a live column the bits did not see);
     //   TM_NZ: listed and not dense-row: the tiles that still need their peers' occupancy words.
     // Row partitions keep neither (another rank's rows arrive only where occupied).
-    sat_used = sat_on;
+    sat_used = p.sat_used;
     last_dense_tiles = 0;
     // push marks ride on the saturation words (an unmarked node's push tiles read as saturated)
-    const bool push_on = sat_on && opt_pull_push != 0 && d_mark[0];
-    bool pushw_any = false;
-    bool short_any = false;  // some listed tile is flagged TM_SHORT (option pull_batch)
+    p.push_on = p.sat_used && opt_pull_push != 0 && d_mark[0];
     // Folded rows (option seen_fold; pull_kernel.h): a sealed tile that is read dense and written whole
     // this tick carries its seen bits in the F_next row (TM_FOLDW), and a tile folded last tick reads
     // them back from F_cur (TM_SEENF).  Only where every tick is one hop of an unmasked, symmetric
     // exchange on one engine (why peers may read folded rows), and never again once
     // a keep mask has dropped receptions (a dropped column would come back out of a folded row).
-    if (keep_any) fold_barred = true;
-    const bool fold_ok = opt_seen_fold != 0 && sat_on && dr_used && !fold_barred && !handshake && !batch &&
+    if (p.keep_any) fold_barred = true;
+    const bool fold_ok = opt_seen_fold != 0 && p.sat_used && p.dr_used && !fold_barred && !handshake && !batch &&
                          !link_timing && opt_rehearse_rows <= 1;
-    // does the launch over the window's words [wb, ..) keep sat bits (run_pull below: tile lists on
-    // the gathering kernel)?
-    auto sat_window = [&](uint32_t wb) {
-        const uint32_t wl = std::min(kPullLdsWords, hw - wb);
-        int lpw = 8;
-        while (lpw < 64 && 2 * lpw < (int)wl) lpw *= 2;
-        if (lpw == 64) return true;  // (a wide window: one peer walk per node)
-        const double avg_deg = n ? (double)nnz / n : 0.0;
-        return !(lpw * 2 <= 64 && 8 < avg_deg);  // (no edge-lanes)
-    };
     if (trace) {
         tr_foldw.assign(hw / kTileWords, 0);
         tr_seenf.assign(hw / kTileWords, 0);
     }
-    fold_launch.assign((hw + kPullLdsWords - 1) / kPullLdsWords, 0);
-    if (sat_used || dr_used) {
+    if (p.sat_used || p.dr_used) {
         if (TM_WORDS * ntw > tmask_cap) {
             HIP_TRY(hipStreamSynchronize(stream));
             const uint32_t cap = TM_WORDS * std::max<uint32_t>(ntw, 8u);
@@ -2271,7 +2311,7 @@ int gossip_engine::tick_step_a(int64_t t) {
             }
             tmask_cap = cap;
         }
-        unsigned long long* TM = h_tmask[slot];
+        unsigned long long* TM = h_tmask[p.slot];
         std::memset(TM, 0, (size_t)TM_WORDS * ntw * 8);
         const uint32_t ntiles = hw / kTileWords;
         // Push-write tiles only when the NEXT tick is expected light: every tile k_pull will list
@@ -2279,12 +2319,12 @@ int gossip_engine::tick_step_a(int64_t t) {
         // enough nodes (push_write) and none turns dense-row.  The k_pull instantiation that reads
         // and writes marks holds more registers (pull_kernel.h PUSH): on a tick with dense tiles
         // (every C4 tick at 2 shards) it costs more than it skips (58.4 -> 60.1 ms per phase).
-        bool light_next = push_on;
-        if (push_on && opt_pull_push != 1) {
+        bool light_next = p.push_on;
+        if (p.push_on && opt_pull_push != 1) {
             for (uint32_t tl = 0; tl < ntiles && light_next; tl++)
                 if (tile_alloc[tl] && !(WF[tl * kTileWords] & WF_YOUNG))
-                    light_next = push_write(tl, t) && !(dr_used && dense_row_hop(tl, t - tile_first[tl]));
-            for (uint32_t i = 0; young && i < ny_leave && light_next; i++)
+                    light_next = push_write(tl, t) && !(p.dr_used && dense_row_hop(tl, t - tile_first[tl]));
+            for (uint32_t i = 0; young && i < p.ny_leave && light_next; i++)
                 light_next = push_write(YP->yt[YP->lv[i]].tile, t);
         }
         for (uint32_t tl = 0; tl < ntiles; tl++) {
@@ -2292,23 +2332,25 @@ int gossip_engine::tick_step_a(int64_t t) {
             const unsigned long long bit = 1ull << (tl & 63u);
             unsigned long long* m = TM + (size_t)TM_WORDS * (tl >> 6);
             const bool fresh = tile_first[tl] == t;
-            const bool dr = dr_used && !fresh && tile_dw[tl] == t - 1;
+            const bool dr = p.dr_used && !fresh && tile_dw[tl] == t - 1;
             if (dr) last_dense_tiles++;
             m[dr ? TM_DENSE : TM_NZ] |= bit;
             // sat bits written by k_pull last tick, no birth since
             const bool clean = !fresh && tile_last_inject[tl] != t - 1 && tile_inj_prev[tl] != t - 1;
-            if (sat_used && clean && tile_satw[tl] == t - 1) m[TM_SATOK] |= bit;
+            if (p.sat_used && clean && tile_satw[tl] == t - 1) m[TM_SATOK] |= bit;
             bool dw = false;
-            if (dr_used && dense_row_hop(tl, t - tile_first[tl])) {  // F_cur's hop next tick
+            if (p.dr_used && dense_row_hop(tl, t - tile_first[tl])) {  // F_cur's hop next tick
                 for (uint32_t q = 0; q < kTileWords; q++) WF[tl * kTileWords + q] |= (uint8_t)WF_DW;
                 tile_dw[tl] = t;
                 dw = true;
             }
             // folded rows: read back what last tick folded; fold again while the tile stays dense and
             // sealed (not open, every member of every instance in it born before this tick)
-            const bool seenf = sat_used && tile_foldw[tl] == t - 1;
+            const bool seenf = p.sat_used && tile_foldw[tl] == t - 1;
             const bool sealed = (int64_t)tl != open_tile && tile_lastborn[tl] < t && tile_last_inject[tl] < t;
-            const bool foldw = fold_ok && dr && dw && sealed && sat_window(tl * kTileWords / kPullLdsWords * kPullLdsWords);
+            PullWindow& win = p.windows[tl * kTileWords / kPullLdsWords];
+            // (the launch over the tile's window keeps sat bits: tile lists on the gathering kernel)
+            const bool foldw = fold_ok && dr && dw && sealed && win.shape.takes_tile_masks();
             if (seenf) m[TM_SEENF] |= bit;
             if (foldw) {
                 m[TM_FOLDW] |= bit;
@@ -2316,7 +2358,7 @@ int gossip_engine::tick_step_a(int64_t t) {
                 tile_folded[tl] = 1;
             }
             if (seenf || foldw) {
-                fold_launch[tl * kTileWords / kPullLdsWords] = 1;
+                win.fold = true;
                 if (trace) {
                     tr_foldw[tl] = foldw;
                     tr_seenf[tl] = seenf;
@@ -2329,98 +2371,256 @@ int gossip_engine::tick_step_a(int64_t t) {
             if (opt_pull_batch && !fresh && tile_cols[tl] &&
                 frontier_entries(tl, t - 1) >= 0.5 * (double)tile_cols[tl]) {
                 m[TM_SHORT] |= bit;
-                short_any = true;
+                p.short_any = true;
             }
             // push marks: the tile's F_cur rows were written by last tick's k_pull alone (listed then
             // with TM_PUSHW, no birth since) -> skipped at unmarked nodes; this tick's rows mark
             // peers when next tick's frontier is expected on few nodes
             // (births of t - 1 into the tile marked their nodes' peers too: k_births)
-            if (push_on && !dr && !fresh && tile_pushw[tl] == t - 1) {
+            if (p.push_on && !dr && !fresh && tile_pushw[tl] == t - 1) {
                 m[TM_PUSH] |= bit;
                 push_tiles++;
             }
             if (light_next && !dw && push_write(tl, t)) {  // (tile_pushw: set by the launch that marks)
                 m[TM_PUSHW] |= bit;
-                pushw_any = true;
+                p.pushw_any = true;
             }
             tile_listed[tl] = t;
         }
-        if (dr_used && young)  // tiles leaving the young set: k_pull_young writes their dense rows
-            for (uint32_t i = 0; i < ny_leave; i++) {
+        if (p.dr_used && young)  // tiles leaving the young set: k_pull_young writes their dense rows
+            for (uint32_t i = 0; i < p.ny_leave; i++) {
                 YoungTile& y = YP->yt[YP->lv[i]];
                 if (dense_row_hop(y.tile, t - tile_first[y.tile])) {
                     y.flags |= (uint8_t)YT_DW;
                     tile_dw[y.tile] = t;
                 }
             }
-        HIP_TRY(hipMemcpyAsync(d_tmask[slot], TM, (size_t)TM_WORDS * ntw * 8, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_tmask[p.slot], TM, (size_t)TM_WORDS * ntw * 8, hipMemcpyHostToDevice, stream));
     }
-    if (!sat_used)  // (set_option refuses what would lead here)
+    if (!p.sat_used)  // (set_option refuses what would lead here)
         for (uint32_t tl = 0; tl < hw / kTileWords; tl++)
             if (tile_alloc[tl] && tile_foldw[tl] == t - 1)
                 return set_error(GOSSIP_ESTATE, "seen_fold: a tile's seen bits are in its frontier rows and this tick's pull keeps no saturation bits");
+    return GOSSIP_OK;
+}
+
+// births [off, off + cnt) of the staged array (all of them, or one row chunk's)
+int gossip_engine::launch_births(const TickPlan& p, uint32_t off, uint32_t cnt) {
+    if (!cnt) return GOSSIP_OK;
+    const int64_t t = p.t;
+    BirthArgs b;
+    b.b = d_births[p.slot] + off; b.nb = cnt; b.gphase = d_gphase[p.slot];
+    b.Fnext = d_F[p.nxt]; b.seen = d_seen; b.stride = stride;
+    b.gen = d_gen; b.recv = d_recv; b.effgen = d_effgen; b.sent = d_sent; b.deg = d_deg;
+    b.live = d_live[p.lv]; b.snap = p.snap_ptr; b.snap_r = p.snap_idx >= 0 ? snaps[p.snap_idx].r : 0;
+    b.nz = d_nz[p.nxt];
+    b.ntw = ntw;
+    b.degc = d_degc;
+    b.slot = (young && p.nwt) ? d_slot[p.nxt] : nullptr;
+    b.cap = young_cap();
+    b.wt = young ? d_young[p.slot]->wt : nullptr;
+    b.nwt = p.nwt;
+    b.rowptr = d_rowptr; b.rev = d_rev;
+    b.hint_next = young ? d_hint[p.nxt] : nullptr;
+    b.stamp_next = hint_stamp(t);
+    b.stamp1_next = hint_stamp1(t);
+    b.sparse_wr = p.skip_wr ? 1u : 0u;
+    b.mark_next = p.pushw_any ? d_mark[t & 1] : nullptr;
+    b.tmask = p.pushw_any ? d_tmask[p.slot] : nullptr;
+    b.col = d_col;
+    b.list = d_ylist;
+    b.list_max = (uint32_t)opt_young_list_cap;
+    b.wt_yid = young ? d_young[p.slot]->wt_yid : nullptr;
+    if (p.fused_tick) {
+        b.FTn = d_FT[p.nxt];
+        b.snz_n = d_snz[(t + 1) % 3];
+        b.kw = n_pad / 32u;
+        b.nstw = snz_nstw;
+    }
+    k_births<<<(cnt + 255) / 256, 256, 0, stream>>>(b);
+    HIP_TRY(hipGetLastError());
+    return GOSSIP_OK;
+}
+
+// end of row chunk c on the engine stream: its exchange may start (exchange_rccl, export)
+int gossip_engine::end_chunk(uint32_t c) {
+    if (!ev_chunk[c]) HIP_TRY(hipEventCreateWithFlags(&ev_chunk[c], hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ev_chunk[c], stream));
+    return GOSSIP_OK;
+}
+
+// blocks for rows [lo, hi): 64 nodes per wave step sequence, 4 waves per block
+uint32_t gossip_engine::grid_for(const TickPlan& p, uint64_t lo, uint64_t hi) const {
+    const uint64_t chunks = (hi - lo + 63) / 64;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((chunks + 3) / 4, pull_grid_cap(p.nt_rows, opt_pull_grid)));
+}
+
+// The pull of rows [base.v0, base.n): one k_pull launch per window of the plan, in the window's
+// shape (pull_plan.h; DENSE mode gathers nothing and never comes here).
+int gossip_engine::run_pull(const TickPlan& p, const PullArgs& base) {
+    const int64_t t = p.t;
+    const uint32_t grid = grid_for(p, base.v0, base.n);
+    for (const PullWindow& win : p.windows) {
+        PullArgs c = base;
+        c.wbase = win.wb;
+        c.wact = win.words;
+        if (p.use_ptile) {
+            c.ptile = d_ptile[p.slot] + win.pt_off;
+            c.nptile = win.pt_cnt;
+        }
+        // saturation bits / dense-row tiles: the gathering kernel (EPN 1) over tile lists
+        size_t extra_lds = 0;
+        if (c.ptile && win.shape.takes_tile_masks() && (p.sat_used || p.dr_used)) {
+            c.tmask = d_tmask[p.slot];
+            c.sat = p.sat_used ? d_sat : nullptr;
+            c.short_batch = p.short_any ? 1u : 0u;
+            c.fold = (p.sat_used && win.fold) ? 1u : 0u;
+            if (p.push_on && pull_sp(win.shape.lpw, win.shape.epn, c)) {  // marks of last tick's push-write rows / this tick's
+                c.mark_cur = mark_tick == t - 1 ? d_mark[(t - 1) & 1] : nullptr;
+                mark_launches += c.mark_cur != nullptr;
+                c.mark_next = p.pushw_any ? d_mark[t & 1] : nullptr;
+                // a tile is read as a push tile next tick only if a launch that marks
+                // covered it (tile_pushw): the mark bitmap then holds every writer's peers
+                if (c.mark_next)
+                    for (uint32_t tl = win.wb / kTileWords; tl < (win.wb + win.words) / kTileWords; tl++)
+                        if ((h_tmask[p.slot][(size_t)TM_WORDS * (tl >> 6) + TM_PUSHW] >> (tl & 63u)) & 1ull) {
+                            tile_pushw[tl] = t;
+                            pushw_tiles++;
+                        }
+            }
+            extra_lds = kPullSatLds + ((c.mark_cur || c.mark_next) ? kPullPushLds : 0);
+            sat_launches += p.sat_used;
+            if (p.sat_used)  // this launch writes the sat bits of its listed tiles
+                for (uint32_t tl = win.wb / kTileWords; tl < (win.wb + win.words) / kTileWords; tl++)
+                    if (tile_listed[tl] == t) tile_satw[tl] = t;
+        }
+        last_lpw = (uint32_t)win.shape.lpw;
+        const size_t lds = pull_lds_bytes(c.wact, c.keep_lds != 0, c.nptile) + extra_lds;
+        if (!launch_pull(win.shape, p.nt_rows, grid, lds, stream, c))
+            return set_error(GOSSIP_EHIP, "k_pull: no instantiation for " + std::to_string(win.shape.lpw) + " word-lanes");
+    }
+    return GOSSIP_OK;
+}
+
+// the young tiles (young_kernel.h) on stream ys, over the graph the pull walks (a.rowptr, a.col)
+int gossip_engine::launch_young(const TickPlan& p, const PullArgs& a, hipStream_t ys) {
+    const int64_t t = p.t;
+    const YoungPack* YP = h_young[p.slot];
+    YoungArgs y;
+    y.rowptr = a.rowptr; y.col = a.col;
+    y.Fcur = d_F[fcur]; y.Fnext = d_F[p.nxt]; y.seen = d_seen;
+    y.slot_cur = d_slot[fcur]; y.slot_next = d_slot[p.nxt];
+    y.ctl = d_ctl[p.slot]; y.wflags = d_wflags[p.slot];
+    y.recv = d_recv; y.live = d_live[p.lv];
+    y.snap = p.snap_ptr; y.acct = d_acct; y.nz_next = d_nz[p.nxt]; y.ntw = ntw;
+    y.yt = d_young[p.slot]->yt; y.ny = p.ny; y.nr = p.ny_read; y.nt = p.ny_leave;
+    y.lv = d_young[p.slot]->lv;
+    y.n = v1; y.v0 = v0; y.stride = stride;
+    y.cap = young_cap();
+    y.hint_cur = d_hint[fcur]; y.hint_next = d_hint[p.nxt]; y.rev = d_rev;
+    y.stamp_cur = hint_stamp(t - 1); y.stamp_next = hint_stamp(t);
+    y.stamp1_cur = hint_stamp1(t - 1); y.stamp1_next = hint_stamp1(t);
+    y.sparse_rd = (skip_wr_last && p.ny_read) ? 1u : 0u;  // (last tick's writers stamped)
+    y.sparse_wr = p.skip_wr ? 1u : 0u;
+    // idle nodes skip the node walk (young_kernel.h) when only stamped slots are read and
+    // every read tile stays young (no list entry is dropped or materialised)
+    bool stay = true;
+    for (uint32_t r = 0; r < p.ny_read; r++) stay &= (YP->yt[r].flags & YT_WRITE) != 0;
+    y.fast = (opt_young_idle != 0 && (y.sparse_rd || !p.ny_read) && stay) ? 1u : 0u;
+    y.work = d_ywork;
+    idle_ticks += y.fast;
+    skip_ticks += y.sparse_rd;
+    y.slot_nt = opt_young_nt ? 1u : 0u;
+    y.list = d_ylist;
+    // (k_pull_young leaves kListReserve entries of the capacity to k_births' appends)
+    y.list_cap = opt_young_list_cap > 2 * (int64_t)kListReserve ? (uint32_t)opt_young_list_cap - kListReserve
+                                                                : (uint32_t)opt_young_list_cap / 2u;
+    y.ymap = d_young[p.slot]->ymap;
+    const uint32_t yg = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>(((uint64_t)(v1 - v0) + 3) / 4,
+                              opt_young_grid > 0 ? (uint64_t)opt_young_grid : 2u * pull_grid_cap(p.nt_rows, opt_pull_grid)));
+    hipEvent_t y0 = nullptr, y1 = nullptr;
+    if (cfg.flags & GOSSIP_F_TIMING) {
+        y0 = get_event();
+        y1 = get_event();
+        HIP_TRY(hipEventRecord(y0, ys));
+    }
+    last_young_grid = yg;
+    if (y.fast) {  // the idle nodes first (young_kernel.h, k_young_idle)
+        const uint64_t nch = ((uint64_t)(v1 - v0) + 63) / 64;
+        k_young_idle<<<(uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nch + 3) / 4, 16384)), 256, 0, ys>>>(y);
+    }
+    if (y.sparse_rd || y.fast || !p.ny_read)
+        k_pull_young<true><<<yg, 256, young_lds_bytes(p.ny, p.ny_read), ys>>>(y);
+    else
+        k_pull_young<false><<<yg, 256, young_lds_bytes(p.ny, p.ny_read), ys>>>(y);
+    HIP_TRY(hipGetLastError());
+    if (cfg.flags & GOSSIP_F_TIMING) {
+        HIP_TRY(hipEventRecord(y1, ys));
+        timers_young.emplace_back(y0, y1);
+    }
+    young_launches++;
+    return GOSSIP_OK;
+}
+
+// DENSE mode: dedup of the incoming words of rows [base.v0, base.n), one node per wave
+// step, the grid sized to the rows (k_dense_dedup, dense_kernel.h)
+void gossip_engine::run_dedup(const PullArgs& base) {
+    const uint64_t rows = base.n > base.v0 ? base.n - base.v0 : 0;
+    const uint32_t g = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>((rows + kDedupWaves - 1) / kDedupWaves, 2u * (uint32_t)num_cus));
+    for (uint32_t wb = 0; wb < hw; wb += kPullLdsWords) {
+        PullArgs c = base;
+        c.wbase = wb;
+        c.wact = std::min(kPullLdsWords, hw - wb);
+        k_dense_dedup<<<g, 64 * kDedupWaves, pull_lds_bytes(c.wact, c.keep_lds != 0), stream>>>(c);
+    }
+}
+
+// the MFMA contraction of rows [lo, hi) (DENSE mode) into the incoming words
+int gossip_engine::run_dense(uint64_t lo, uint64_t hi, const unsigned long long* live_prev) {
+    BitsArgs gm;
+    gm.Ab = d_Ab; gm.FT = d_FT[fcur]; gm.inc = d_inc; gm.live_prev = live_prev; gm.acct = d_acct;
+    gm.n = (uint32_t)hi; gm.n_pad = n_pad; gm.kw = n_pad / 32u; gm.stride = stride;
+    gm.mb0 = (uint32_t)lo / kDenseTile;  // row partition: this engine's row blocks only
+    gm.mb = (std::min((uint32_t)hi + kDenseTile - 1u, n_pad) - (uint32_t)lo) / kDenseTile;
+    gm.nt = hw / 4u;
+    const uint32_t nst = n_pad / kStageK;
+    uint32_t ks = 1;  // split K until the chip has ~2 tiles per CU (>= 2 stages per split)
+    const uint64_t min_tiles = (uint64_t)std::max<int64_t>(1, opt_dense_min_tiles);
+    while ((uint64_t)gm.mb * gm.nt * ks < min_tiles && ks * 4 <= nst) ks *= 2;
+    gm.ksplit = ks;
+    gm.total = gm.mb * gm.nt * ks;
+    k_dense_bits<<<(gm.total + 7u) / 8u * 8u, 512, 0, stream>>>(gm);
+    HIP_TRY(hipGetLastError());
+    return GOSSIP_OK;
+}
+
+int gossip_engine::launch_tick(TickPlan& p) {
+    const int64_t t = p.t;
+    const int slot = p.slot;
+    const uint32_t nb = p.nb, ny = p.ny;
     // 5. upload + launches
     const uint32_t wact = hw;
-    if (wact) HIP_TRY(hipMemcpyAsync(d_ctl[slot], C, (size_t)wact * sizeof(WordCtl), hipMemcpyHostToDevice, stream));
-    if (wact) HIP_TRY(hipMemcpyAsync(d_wflags[slot], WF, (size_t)wact, hipMemcpyHostToDevice, stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(d_births[slot], B, (size_t)nb * sizeof(Birth), hipMemcpyHostToDevice, stream));
-    if (np) HIP_TRY(hipMemcpyAsync(d_gphase[slot], GP, (size_t)np * 4, hipMemcpyHostToDevice, stream));
-    if (smask_any) HIP_TRY(hipMemcpyAsync(d_smask[slot], h_smask[slot], nsnap * hw * 8, hipMemcpyHostToDevice, stream));
-    if (ny) HIP_TRY(hipMemcpyAsync(d_young[slot], YP, sizeof(YoungPack), hipMemcpyHostToDevice, stream));
+    if (wact) HIP_TRY(hipMemcpyAsync(d_ctl[slot], h_ctl[slot], (size_t)wact * sizeof(WordCtl), hipMemcpyHostToDevice, stream));
+    if (wact) HIP_TRY(hipMemcpyAsync(d_wflags[slot], h_wflags[slot], (size_t)wact, hipMemcpyHostToDevice, stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(d_births[slot], h_births[slot], (size_t)nb * sizeof(Birth), hipMemcpyHostToDevice, stream));
+    if (p.np) HIP_TRY(hipMemcpyAsync(d_gphase[slot], h_gphase[slot], (size_t)p.np * 4, hipMemcpyHostToDevice, stream));
+    if (p.smask_any) HIP_TRY(hipMemcpyAsync(d_smask[slot], h_smask[slot], p.nsnap * hw * 8, hipMemcpyHostToDevice, stream));
+    if (ny) HIP_TRY(hipMemcpyAsync(d_young[slot], h_young[slot], sizeof(YoungPack), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(slot_done[slot], stream));
-    const int lv = (int)(t % 3);
+    p.lv = (int)(t % 3);
+    p.nxt = fcur ^ 1;
+    p.snap_ptr = p.snap_idx >= 0 ? d_scalars + 2 + 2 * p.snap_idx + 1 : nullptr;
+    const int lv = p.lv, nxt = p.nxt;
     if (wact) HIP_TRY(hipMemsetAsync(d_live[lv], 0, (size_t)wact * 8, stream));
-    unsigned long long* snap_ptr = snap_idx >= 0 ? d_scalars + 2 + 2 * snap_idx + 1 : nullptr;
-    const int nxt = fcur ^ 1;
     // DENSE ticks run k_dense_fused (dense_kernel.h) unless the tick has id groups, row chunks
     // (row partition: other ranks' rows reach F_next without FT), or the diagnostic no-skip pull
-    const bool fused_tick = dense && wact && opt_dense_fused && nchunks == 1 && (row_count == 1 || fused_rows) &&
-                            !(cfg.flags & GOSSIP_F_NOSKIP) && !group_any && ntw <= kFActWords &&
-                            (uint64_t)(wact / 4u) * (n_pad / kStageK) < (1ull << 20);  // (its packed unit scan)
-    if (fused_rows && wact && !fused_tick)  // (the other ranks' F rows are not exchanged)
+    p.fused_tick = dense && wact && opt_dense_fused && nchunks == 1 && (row_count == 1 || fused_rows) &&
+                   !(cfg.flags & GOSSIP_F_NOSKIP) && !p.group_any && ntw <= kFActWords &&
+                   (uint64_t)(wact / 4u) * (n_pad / kStageK) < (1ull << 20);  // (its packed unit scan)
+    if (fused_rows && wact && !p.fused_tick)  // (the other ranks' F rows are not exchanged)
         return set_error(GOSSIP_ECAPACITY, "fused row partition: the window outgrew the fused kernel (<= 4,096 words)");
-    // births [off, off + cnt) of the staged array (all of them, or one row chunk's)
-    auto launch_births = [&](uint32_t off, uint32_t cnt) -> int {
-        if (!cnt) return GOSSIP_OK;
-        BirthArgs b;
-        b.b = d_births[slot] + off; b.nb = cnt; b.gphase = d_gphase[slot];
-        b.Fnext = d_F[nxt]; b.seen = d_seen; b.stride = stride;
-        b.gen = d_gen; b.recv = d_recv; b.effgen = d_effgen; b.sent = d_sent; b.deg = d_deg;
-        b.live = d_live[lv]; b.snap = snap_ptr; b.snap_r = snap_idx >= 0 ? snaps[snap_idx].r : 0;
-        b.nz = d_nz[nxt];
-        b.ntw = ntw;
-        b.degc = d_degc;
-        b.slot = (young && nwt) ? d_slot[nxt] : nullptr;
-        b.cap = (uint32_t)std::min<int64_t>(kSlotU16 - 1, std::max<int64_t>(1, opt_young_cap));
-        b.wt = young ? d_young[slot]->wt : nullptr;
-        b.nwt = nwt;
-        b.rowptr = d_rowptr; b.rev = d_rev;
-        b.hint_next = young ? d_hint[nxt] : nullptr;
-        b.stamp_next = hint_stamp(t);
-        b.stamp1_next = hint_stamp1(t);
-        b.sparse_wr = skip_wr ? 1u : 0u;
-        b.mark_next = pushw_any ? d_mark[t & 1] : nullptr;
-        b.tmask = pushw_any ? d_tmask[slot] : nullptr;
-        b.col = d_col;
-        b.list = d_ylist;
-        b.list_max = (uint32_t)opt_young_list_cap;
-        b.wt_yid = young ? d_young[slot]->wt_yid : nullptr;
-        if (fused_tick) {
-            b.FTn = d_FT[nxt];
-            b.snz_n = d_snz[(t + 1) % 3];
-            b.kw = n_pad / 32u;
-            b.nstw = snz_nstw;
-        }
-        k_births<<<(cnt + 255) / 256, 256, 0, stream>>>(b);
-        HIP_TRY(hipGetLastError());
-        return GOSSIP_OK;
-    };
-    // end of row chunk c on the engine stream: its exchange may start (exchange_rccl, export)
-    auto end_chunk = [&](uint32_t c) -> int {
-        if (!ev_chunk[c]) HIP_TRY(hipEventCreateWithFlags(&ev_chunk[c], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_chunk[c], stream));
-        return GOSSIP_OK;
-    };
     if (wact) {
         PullArgs a;
         a.rowptr = d_rowptr; a.col = d_col;
@@ -2430,7 +2630,7 @@ int gossip_engine::tick_step_a(int64_t t) {
         }
         a.Fcur = d_F[fcur]; a.Fnext = d_F[nxt]; a.seen = d_seen; a.ctl = d_ctl[slot];
         a.wflags = d_wflags[slot];
-        a.recv = d_recv; a.live = d_live[lv]; a.snap = snap_ptr;
+        a.recv = d_recv; a.live = d_live[lv]; a.snap = p.snap_ptr;
         a.live_prev = (t - 1 >= tick0) ? d_live[(t - 1) % 3] : nullptr;
         a.acct = d_acct;
         a.nz_cur = d_nz[fcur];
@@ -2439,72 +2639,13 @@ int gossip_engine::tick_step_a(int64_t t) {
         a.n = v1; a.stride = stride; a.wbase = 0; a.wact = wact;
         a.v0 = v0;  // row partition: this engine's rows [v0, v1)
         a.noskip = (cfg.flags & GOSSIP_F_NOSKIP) ? 1u : 0u;
-        a.keep_lds = keep_any ? 1u : 0u;
+        a.keep_lds = p.keep_any ? 1u : 0u;
         a.gate_seen = opt_pull_gate ? 1u : 0u;
         // non-temporal rows iff the frontier the launch gathers from (n rows x wact live words)
         // exceeds kPullNtBytes
-        const bool nt_rows = opt_pull_nt >= 0 ? opt_pull_nt == 1 : (uint64_t)n * wact * 8u > kPullNtBytes;
-        // blocks for rows [lo, hi): 64 nodes per wave step sequence, 4 waves per block
-        auto grid_for = [&](uint64_t lo, uint64_t hi) {
-            const uint64_t chunks = (hi - lo + 63) / 64;
-            return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((chunks + 3) / 4, pull_grid_cap(nt_rows, opt_pull_grid)));
-        };
-        const uint32_t grid = grid_for(v0, v1);
-        last_nt = nt_rows ? 1u : 0u;
-        last_grid = grid;
-        const double avg_deg = n ? (double)nnz / n : 0.0;
-        // One launch per kPullLdsWords words of the window (its per-word state lives in LDS).
-        // Lane layout: word-lanes cover the launch's words in one pass when possible (at least
-        // the 8 word-pairs of one tile); spare lanes of the wave split the peer list
-        // (edge-lanes) when peers are many -- and never in DENSE mode, which gathers nothing.
-        auto run_pull = [&](const PullArgs& base, bool split_edges) {
-            const uint32_t grid = grid_for(base.v0, base.n);
-            for (uint32_t wb = 0, li = 0; wb < wact; wb += kPullLdsWords, li++) {
-                PullArgs c = base;
-                c.wbase = wb;
-                c.wact = std::min(kPullLdsWords, wact - wb);
-                if (use_ptile && split_edges && li < pt_off.size()) {
-                    c.ptile = d_ptile[slot] + pt_off[li];
-                    c.nptile = pt_cnt[li];
-                }
-                int lpw = 8;
-                while (lpw < 64 && 2 * lpw < (int)c.wact) lpw *= 2;
-                // windows wider than 64 words keep one peer walk per node (the pipelined path)
-                const bool wide_window = lpw == 64 && split_edges;
-                if (wide_window) lpw = kWideLanes;
-                int epn = 1;
-                while (split_edges && !wide_window && lpw * epn * 2 <= 64 && epn * 8 < avg_deg) epn *= 2;
-                // saturation bits / dense-row tiles: the gathering kernel (EPN 1) over tile lists
-                size_t extra_lds = 0;
-                if (c.ptile && epn == 1 && (sat_used || dr_used)) {
-                    c.tmask = d_tmask[slot];
-                    c.sat = sat_used ? d_sat : nullptr;
-                    c.short_batch = short_any ? 1u : 0u;
-                    c.fold = (sat_used && li < fold_launch.size() && fold_launch[li]) ? 1u : 0u;
-                    if (push_on && pull_sp(lpw, epn, c)) {  // marks of last tick's push-write rows / this tick's
-                        c.mark_cur = mark_tick == t - 1 ? d_mark[(t - 1) & 1] : nullptr;
-                        mark_launches += c.mark_cur != nullptr;
-                        c.mark_next = pushw_any ? d_mark[t & 1] : nullptr;
-                        // a tile is read as a push tile next tick only if a launch that marks
-                        // covered it (tile_pushw): the mark bitmap then holds every writer's peers
-                        if (c.mark_next)
-                            for (uint32_t tl = wb / kTileWords; tl < (wb + c.wact) / kTileWords; tl++)
-                                if ((h_tmask[slot][(size_t)TM_WORDS * (tl >> 6) + TM_PUSHW] >> (tl & 63u)) & 1ull) {
-                                    tile_pushw[tl] = t;
-                                    pushw_tiles++;
-                                }
-                    }
-                    extra_lds = kPullSatLds + ((c.mark_cur || c.mark_next) ? kPullPushLds : 0);
-                    sat_launches += sat_used;
-                    if (sat_used)  // this launch writes the sat bits of its listed tiles
-                        for (uint32_t tl = wb / kTileWords; tl < (wb + c.wact) / kTileWords; tl++)
-                            if (tile_listed[tl] == t) tile_satw[tl] = t;
-                }
-                last_lpw = (uint32_t)lpw;
-                const size_t lds = pull_lds_bytes(c.wact, c.keep_lds != 0, c.nptile) + extra_lds;
-                launch_pull(lpw, epn, nt_rows, grid, lds, stream, c);
-            }
-        };
+        p.nt_rows = opt_pull_nt >= 0 ? opt_pull_nt == 1 : (uint64_t)n * wact * 8u > kPullNtBytes;
+        last_nt = p.nt_rows ? 1u : 0u;
+        last_grid = grid_for(p, v0, v1);
         hipEvent_t e0 = nullptr, e1 = nullptr, p0 = nullptr, p1 = nullptr;
         a.inc = nullptr;
         // DENSE phase = transpose + MFMA + dedup, timed as ONE unit (below)
@@ -2515,16 +2656,16 @@ int gossip_engine::tick_step_a(int64_t t) {
         unsigned long long* pts = dense_timing ? d_phase_ts : nullptr;
         // a fused tick after a three-kernel one: the stage masks it writes were not zeroed, and
         // k_transpose builds the ones it reads
-        if (fused_tick && !ft_valid)
+        if (p.fused_tick && !ft_valid)
             for (int64_t k = 0; k < 2; k++)
                 HIP_TRY(hipMemsetAsync(d_snz[(t + k) % 3], 0, (size_t)(stride / 4u) * snz_nstw * 8u, stream));
         if (pts) k_phase_start<<<1, 1, 0, stream>>>(pts);
-        if (dense && !(fused_tick && ft_valid)) {
+        if (dense && !(p.fused_tick && ft_valid)) {
             // transpose the frontier to share-column bit rows (the fused path's FT[fcur] was
             // written by the last tick's k_dense_fused + k_births)
             dim3 eg(n_pad / 256u, wact);
             k_transpose<<<eg, 256, 0, stream>>>(d_F[fcur], stride, n, n_pad / 32u, wact, a.live_prev,
-                                                d_nz[fcur], ntw, d_FT[fcur], fused_tick ? d_snz[t % 3] : nullptr,
+                                                d_nz[fcur], ntw, d_FT[fcur], p.fused_tick ? d_snz[t % 3] : nullptr,
                                                 snz_nstw);
             HIP_TRY(hipGetLastError());
         }
@@ -2542,11 +2683,11 @@ int gossip_engine::tick_step_a(int64_t t) {
             }
             HIP_TRY(hipMemsetAsync(d_nz[nxt] + (uint64_t)v0 * ntw, 0, (size_t)(v1 - v0) * ntw * 8u, stream));
             a.shared_out = 1u;
-        } else if (use_ptile) {
+        } else if (p.use_ptile) {
             // k_pull writes whole occupancy words only for the words its listed tiles fall in
             HIP_TRY(hipMemsetAsync(d_nz[nxt] + (uint64_t)v0 * ntw, 0, (size_t)(v1 - v0) * ntw * 8u, stream));
         }
-        if (pushw_any)  // this tick's push marks start empty (last read by the pull of t - 1)
+        if (p.pushw_any)  // this tick's push marks start empty (last read by the pull of t - 1)
             HIP_TRY(hipMemsetAsync(d_mark[t & 1], 0, ((size_t)n + 64) / 64 * 8, stream));
         if (cfg.flags & GOSSIP_F_TIMING) {
             e0 = get_event();
@@ -2557,94 +2698,6 @@ int gossip_engine::tick_step_a(int64_t t) {
                 HIP_TRY(hipEventRecord(p0, stream));
             }
         }
-        auto launch_young = [&](hipStream_t ys) -> int {
-            YoungArgs y;
-            y.rowptr = a.rowptr; y.col = a.col;
-            y.Fcur = d_F[fcur]; y.Fnext = d_F[nxt]; y.seen = d_seen;
-            y.slot_cur = d_slot[fcur]; y.slot_next = d_slot[nxt];
-            y.ctl = d_ctl[slot]; y.wflags = d_wflags[slot];
-            y.recv = d_recv; y.live = d_live[lv];
-            y.snap = snap_ptr; y.acct = d_acct; y.nz_next = d_nz[nxt]; y.ntw = ntw;
-            y.yt = d_young[slot]->yt; y.ny = ny; y.nr = ny_read; y.nt = ny_leave;
-            y.lv = d_young[slot]->lv;
-            y.n = v1; y.v0 = v0; y.stride = stride;
-            y.cap = (uint32_t)std::min<int64_t>(kSlotU16 - 1, std::max<int64_t>(1, opt_young_cap));
-            y.hint_cur = d_hint[fcur]; y.hint_next = d_hint[nxt]; y.rev = d_rev;
-            y.stamp_cur = hint_stamp(t - 1); y.stamp_next = hint_stamp(t);
-            y.stamp1_cur = hint_stamp1(t - 1); y.stamp1_next = hint_stamp1(t);
-            y.sparse_rd = (skip_wr_last && ny_read) ? 1u : 0u;  // (last tick's writers stamped)
-            y.sparse_wr = skip_wr ? 1u : 0u;
-            // idle nodes skip the node walk (young_kernel.h) when only stamped slots are read and
-            // every read tile stays young (no list entry is dropped or materialised)
-            bool stay = true;
-            for (uint32_t r = 0; r < ny_read; r++) stay &= (YP->yt[r].flags & YT_WRITE) != 0;
-            y.fast = (opt_young_idle != 0 && (y.sparse_rd || !ny_read) && stay) ? 1u : 0u;
-            y.work = d_ywork;
-            idle_ticks += y.fast;
-            skip_ticks += y.sparse_rd;
-            y.slot_nt = opt_young_nt ? 1u : 0u;
-            y.list = d_ylist;
-            // (k_pull_young leaves kListReserve entries of the capacity to k_births' appends)
-            y.list_cap = opt_young_list_cap > 2 * (int64_t)kListReserve ? (uint32_t)opt_young_list_cap - kListReserve
-                                                                        : (uint32_t)opt_young_list_cap / 2u;
-            y.ymap = d_young[slot]->ymap;
-            const uint32_t yg = (uint32_t)std::max<uint64_t>(
-                1, std::min<uint64_t>(((uint64_t)(v1 - v0) + 3) / 4,
-                                      opt_young_grid > 0 ? (uint64_t)opt_young_grid : 2u * pull_grid_cap(nt_rows, opt_pull_grid)));
-            hipEvent_t y0 = nullptr, y1 = nullptr;
-            if (cfg.flags & GOSSIP_F_TIMING) {
-                y0 = get_event();
-                y1 = get_event();
-                HIP_TRY(hipEventRecord(y0, ys));
-            }
-            last_young_grid = yg;
-            if (y.fast) {  // the idle nodes first (young_kernel.h, k_young_idle)
-                const uint64_t nch = ((uint64_t)(v1 - v0) + 63) / 64;
-                k_young_idle<<<(uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nch + 3) / 4, 16384)), 256, 0, ys>>>(y);
-            }
-            if (y.sparse_rd || y.fast || !ny_read)
-                k_pull_young<true><<<yg, 256, young_lds_bytes(ny, ny_read), ys>>>(y);
-            else
-                k_pull_young<false><<<yg, 256, young_lds_bytes(ny, ny_read), ys>>>(y);
-            HIP_TRY(hipGetLastError());
-            if (cfg.flags & GOSSIP_F_TIMING) {
-                HIP_TRY(hipEventRecord(y1, ys));
-                timers_young.emplace_back(y0, y1);
-            }
-            young_launches++;
-            return GOSSIP_OK;
-        };
-        // DENSE mode: dedup of the incoming words of rows [base.v0, base.n), one node per wave
-        // step, the grid sized to the rows (k_dense_dedup, dense_kernel.h)
-        auto run_dedup = [&](const PullArgs& base) {
-            const uint64_t rows = base.n > base.v0 ? base.n - base.v0 : 0;
-            const uint32_t g = (uint32_t)std::max<uint64_t>(
-                1, std::min<uint64_t>((rows + kDedupWaves - 1) / kDedupWaves, 2u * (uint32_t)num_cus));
-            for (uint32_t wb = 0; wb < wact; wb += kPullLdsWords) {
-                PullArgs c = base;
-                c.wbase = wb;
-                c.wact = std::min(kPullLdsWords, wact - wb);
-                k_dense_dedup<<<g, 64 * kDedupWaves, pull_lds_bytes(c.wact, c.keep_lds != 0), stream>>>(c);
-            }
-        };
-        // the MFMA contraction of rows [lo, hi) (DENSE mode) into the incoming words
-        auto run_dense = [&](uint64_t lo, uint64_t hi) -> int {
-            BitsArgs gm;
-            gm.Ab = d_Ab; gm.FT = d_FT[fcur]; gm.inc = d_inc; gm.live_prev = a.live_prev; gm.acct = d_acct;
-            gm.n = (uint32_t)hi; gm.n_pad = n_pad; gm.kw = n_pad / 32u; gm.stride = stride;
-            gm.mb0 = (uint32_t)lo / kDenseTile;  // row partition: this engine's row blocks only
-            gm.mb = (std::min((uint32_t)hi + kDenseTile - 1u, n_pad) - (uint32_t)lo) / kDenseTile;
-            gm.nt = wact / 4u;
-            const uint32_t nst = n_pad / kStageK;
-            uint32_t ks = 1;  // split K until the chip has ~2 tiles per CU (>= 2 stages per split)
-            const uint64_t min_tiles = (uint64_t)std::max<int64_t>(1, opt_dense_min_tiles);
-            while ((uint64_t)gm.mb * gm.nt * ks < min_tiles && ks * 4 <= nst) ks *= 2;
-            gm.ksplit = ks;
-            gm.total = gm.mb * gm.nt * ks;
-            k_dense_bits<<<(gm.total + 7u) / 8u * 8u, 512, 0, stream>>>(gm);
-            HIP_TRY(hipGetLastError());
-            return GOSSIP_OK;
-        };
         if (nchunks > 1) {
             // Pipelined exchange: pull (+ the MFMA contraction) and births per row chunk, each
             // chunk closed by its event so that its exchange overlaps the next chunk.  Timed as
@@ -2661,24 +2714,25 @@ int gossip_engine::tick_step_a(int64_t t) {
                     ac.v0 = (uint32_t)lo;
                     ac.n = (uint32_t)hi;
                     if (dense) {
-                        const int rc = run_dense(lo, hi);
+                        const int rc = run_dense(lo, hi, a.live_prev);
                         if (rc) return rc;
                         if (timing) HIP_TRY(hipEventRecord(c1, stream));
                         ac.inc = d_inc;
                         run_dedup(ac);
                     } else {
-                        run_pull(ac, true);
+                        const int rc = run_pull(p, ac);
+                        if (rc) return rc;
                         if (timing) HIP_TRY(hipEventRecord(c1, stream));
                     }
                     if (timing) timers.emplace_back(c0, c1);
                 }
-                int rc = launch_births(cb_off[c], cb_off[c + 1] - cb_off[c]);
+                int rc = launch_births(p, p.cb_off[c], p.cb_off[c + 1] - p.cb_off[c]);
                 if (rc) return rc;
                 if ((rc = end_chunk(c))) return rc;
             }
             if (pts) k_phase_acc<<<1, 1, 0, stream>>>(pts);  // (row chunks: the chunks' births are inside the span)
             if (p0) event_pool.push_back(p0);  // (timed per chunk above)
-        } else if (fused_tick) {
+        } else if (p.fused_tick) {
             // the whole DENSE pull in one persistent kernel (contraction, dedup, FT of F_next)
             FusedArgs f;
             // a row rank: its rows [v0, v1) (row blocks of 256 from v0 / 256; v0 is 512-aligned)
@@ -2691,7 +2745,7 @@ int gossip_engine::tick_step_a(int64_t t) {
             f.snz_z = d_snz[(t + 2) % 3];
             f.snz_zwords = (stride / 4u) * snz_nstw;
             f.seen = d_seen + r0 * stride; f.Fnext = d_F[nxt] + r0 * stride; f.ctl = d_ctl[slot]; f.wflags = d_wflags[slot];
-            f.recv = d_recv + r0; f.live = d_live[lv]; f.live_prev = a.live_prev; f.snap = snap_ptr; f.acct = d_acct;
+            f.recv = d_recv + r0; f.live = d_live[lv]; f.live_prev = a.live_prev; f.snap = p.snap_ptr; f.acct = d_acct;
             f.nz_next = d_nz[nxt] + r0 * ntw; f.ntw = ntw;
             f.n = rows; f.n_pad = n_pad; f.kw = n_pad / 32u; f.stride = stride;
             f.nst = n_pad / kStageK; f.nstw = snz_nstw;
@@ -2719,7 +2773,7 @@ int gossip_engine::tick_step_a(int64_t t) {
             // The timed kernel in DENSE mode is the MFMA contraction (pull_ms); its incoming
             // words are then consumed by k_dense_dedup.  The whole phase -- transpose, MFMA,
             // dedup -- is timed as pull_phase_ms.
-            const int rc = run_dense(v0, v1);
+            const int rc = run_dense(v0, v1, a.live_prev);
             if (rc) return rc;
             if (cfg.flags & GOSSIP_F_TIMING) {
                 HIP_TRY(hipEventRecord(e1, stream));
@@ -2741,7 +2795,8 @@ int gossip_engine::tick_step_a(int64_t t) {
                     rb = get_event();
                     HIP_TRY(hipEventRecord(ra, stream));
                 }
-                run_pull(ar, true);
+                const int rc = run_pull(p, ar);
+                if (rc) return rc;
                 if (cfg.flags & GOSSIP_F_TIMING) {
                     HIP_TRY(hipEventRecord(rb, stream));
                     rr_events.push_back({r, 0u, ra, rb});
@@ -2756,10 +2811,11 @@ int gossip_engine::tick_step_a(int64_t t) {
             if (overlap) {
                 HIP_TRY(hipEventRecord(ev_fork, stream));
                 HIP_TRY(hipStreamWaitEvent(ystream, ev_fork, 0));
-                const int rc = launch_young(ystream);
+                const int rc = launch_young(p, a, ystream);
                 if (rc) return rc;
             }
-            run_pull(a, true);
+            const int rc = run_pull(p, a);
+            if (rc) return rc;
             if (cfg.flags & GOSSIP_F_TIMING) {
                 HIP_TRY(hipEventRecord(e1, stream));
                 timers.emplace_back(e0, e1);
@@ -2768,7 +2824,7 @@ int gossip_engine::tick_step_a(int64_t t) {
                 HIP_TRY(hipEventRecord(ev_join, ystream));
                 HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
             } else if (ny) {  // the young tiles (young_kernel.h), after k_pull wrote the nz words
-                const int rc = launch_young(stream);
+                const int rc = launch_young(p, a, stream);
                 if (rc) return rc;
             }
             if (p0 && (cfg.flags & GOSSIP_F_TIMING)) {  // the whole pull phase
@@ -2783,28 +2839,28 @@ int gossip_engine::tick_step_a(int64_t t) {
     }
     if (nchunks == 1 || !wact) {  // (chunked ticks with live words launched them per chunk)
         for (uint32_t c = 0; c < nchunks; c++) {
-            int rc = launch_births(nchunks == 1 ? 0u : cb_off[c], nchunks == 1 ? nb : cb_off[c + 1] - cb_off[c]);
+            int rc = launch_births(p, nchunks == 1 ? 0u : p.cb_off[c], nchunks == 1 ? nb : p.cb_off[c + 1] - p.cb_off[c]);
             if (rc) return rc;
             if ((rc = end_chunk(c))) return rc;
         }
     }
     if (young) {  // F_next's slots hold this tick's write-sparse tiles: next tick reads them
-        tile_widx.swap(new_widx);
-        wt_last.assign(YP->wt, YP->wt + nwt);
-        skip_wr_last = skip_wr && ny && wact;  // (stamped only if this tick launched the young kernel)
+        tile_widx.swap(p.new_widx);
+        wt_last.assign(h_young[slot]->wt, h_young[slot]->wt + p.nwt);
+        skip_wr_last = p.skip_wr && ny && wact;  // (stamped only if this tick launched the young kernel)
     }
-    if (smask_any) {  // hop-batched snapshots: arrivals of this tick that precede each snapshot
+    if (p.smask_any) {  // hop-batched snapshots: arrivals of this tick that precede each snapshot
         const uint64_t cells = (uint64_t)(v1 - v0) * hw;
         const uint32_t g = (uint32_t)std::min<uint64_t>((cells + 255) / 256, 4096);
-        for (uint32_t s0 = 0; s0 < nsnap; s0 += kSnapGroup) {
+        for (uint32_t s0 = 0; s0 < p.nsnap; s0 += kSnapGroup) {
             k_snap_count<<<g, 256, 0, stream>>>(d_F[nxt] + (uint64_t)v0 * stride, d_nz[nxt] + (uint64_t)v0 * ntw,
                                                 stride, ntw, v1 - v0, hw, d_smask[slot], s0,
-                                                (uint32_t)std::min<size_t>(kSnapGroup, nsnap - s0), d_scalars);
+                                                (uint32_t)std::min<size_t>(kSnapGroup, p.nsnap - s0), d_scalars);
             HIP_TRY(hipGetLastError());
         }
     }
-    ft_valid = fused_tick;  // FT[nxt] / d_snz[(t + 1) % 3] describe the next tick's F_cur
-    if (pushw_any && wact) mark_tick = t;  // (d_mark[t & 1] holds this tick's marks)
+    ft_valid = p.fused_tick;  // FT[nxt] / d_snz[(t + 1) % 3] describe the next tick's F_cur
+    if (p.pushw_any && wact) mark_tick = t;  // (d_mark[t & 1] holds this tick's marks)
     return GOSSIP_OK;
 }
 
