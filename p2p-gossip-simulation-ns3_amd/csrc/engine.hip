@@ -443,6 +443,7 @@ __global__ __launch_bounds__(256) void k_births(BirthArgs a) {
     if (x.kind == BIRTH_NOOP) return;
     if (x.kind == BIRTH_LOST) {  // sent behind the REGISTER segment (:178): lost, id processed
         a.effgen[v] += 1u;
+        if (a.snap && x.phase < a.snap_r) atomicAdd(a.snap, 1ull);
         return;
     }
     const uint32_t w = x.col >> 6;

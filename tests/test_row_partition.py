@@ -49,6 +49,8 @@ def test_group_run_matches_single_engine_and_oracle(gossip, oracle, mode, n, p, 
     topo, t_cut, ev = _inputs(gossip, n, p, 31, 7.3)
     m = gossip.MODE_DENSE if mode.startswith("dense") else gossip.MODE_CSR
     flags = gossip.F_HOP_BATCH if batch else 0
+    # (tick boundaries at 5 ms: each rank's base sums over its own rows, no in-tick partial; snapshots
+    #  inside a tick, against ORACLE A: test_snapshots_gpu.py)
     snaps = [gossip.seconds_to_ns(6.0), gossip.seconds_to_ns(7.0)]
     ref = _engine(gossip, n, t_cut, topo, ev, m, flags, snaps=snaps)
     ref.run()

@@ -120,7 +120,9 @@ def test_young_dense_graph(gossip, oracle):
 
 
 def test_young_periodic_snapshots(gossip, oracle, monkeypatch):
-    # PrintPeriodicStats partials counted inside k_pull_young (WF_SNAP) and k_births
+    # PrintPeriodicStats rows of a young-tile run.  10 s and 20 s are tick boundaries at 5 ms, so these
+    # snapshots are the base sums over the ticks before them; the partials counted inside k_pull_young
+    # (WF_SNAP) and k_births belong to in-tick snapshot times: test_snapshots_gpu.py
     monkeypatch.setenv("GOSSIP_YOUNG", "1")
     monkeypatch.setenv("GOSSIP_YOUNG_CAP", "5")
     # (21 s: the snapshots at 10 s and 20 s, the second one inside the young-tile regime)
@@ -158,7 +160,8 @@ def test_young_dense_rows(gossip, oracle, case):
 
 
 def test_young_dense_rows_periodic_snapshots(gossip, oracle, monkeypatch):
-    # periodic snapshot partials with dense-row tiles and saturation bits in play
+    # periodic snapshots with dense-row tiles and saturation bits in play (tick-aligned times: the base
+    # sums only; in-tick partials: test_snapshots_gpu.py)
     monkeypatch.setenv("GOSSIP_YOUNG", "1")
     monkeypatch.setenv("GOSSIP_DENSE_ROWS", "1")
     sim = gossip.P2PGossipNetworkSimulation(1200, topo_seed=77, node_seed=78, flags=gossip.F_TILE_PER_TICK)
