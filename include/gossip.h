@@ -468,6 +468,51 @@ int gossip_engine_get_rehearsal(gossip_engine* e, uint32_t ranges, double* pull_
 int gossip_engine_get_rehearsal_peak(gossip_engine* e, uint32_t ranges, uint64_t* msg_bytes_max);
 int gossip_engine_reset_timing(gossip_engine* e);
 
+/* Launch ledger: what the engine launched, by (kernel, variant), counted on the host where each
+ * kernel is launched -- for k_pull from the template arguments of the instantiation at its launch
+ * site, so a record says which compiled kernel ran, not which one the shape rule would pick.
+ * Cumulative since gossip_engine_create; gossip_engine_reset_timing does not clear it.
+ *   kernel    GOSSIP_K_*
+ *   lpw, epn  k_pull: word-lanes and edge-lanes per node (0 for the other kernels)
+ *   flags     k_pull: GOSSIP_PULL_* template flags (0 for the other kernels)
+ *   arg       k_pull_young: its template argument (1: the sparse-tick instantiation);
+ *             k_dense_bits: the K split (ksplit); 0 otherwise
+ *   launches  launches of that variant
+ *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's
+ *             grid-stride loop ran more than once: k_pull, k_pull_young and k_young_idle 4 x blocks <
+ *             ceil(rows / 64) chunks; k_dense_dedup 16 x blocks < rows.  k_dense_bits has no such
+ *             loop: there it counts launches with an UNEVEN K split, stages % ksplit != 0 (stages =
+ *             n_pad / 1,024; split z takes ceil(stages / ksplit) stages from its start, the last
+ *             non-empty one fewer), which includes every launch with an empty split. */
+#define GOSSIP_K_PULL 0
+#define GOSSIP_K_PULL_YOUNG 1
+#define GOSSIP_K_YOUNG_IDLE 2
+#define GOSSIP_K_DENSE_BITS 3
+#define GOSSIP_K_DENSE_DEDUP 4
+#define GOSSIP_PULL_NT 1u     /* non-temporal row accesses                  */
+#define GOSSIP_PULL_SP 2u     /* tile masks, saturation bits (32 x 1 lanes) */
+#define GOSSIP_PULL_PUSH 4u   /* push marks                                 */
+#define GOSSIP_PULL_SHORT 8u  /* batch schedule of exit-likely passes       */
+#define GOSSIP_PULL_FOLD 16u  /* folded rows (option seen_fold)             */
+typedef struct gossip_launch_record {
+    uint32_t kernel;
+    uint32_t lpw;
+    uint32_t epn;
+    uint32_t flags;
+    uint32_t arg;
+    uint32_t pad0;
+    uint64_t launches;
+    uint64_t strided;
+} gossip_launch_record;
+/* The ledger's records in first-launch order.  *count = the number of records; out = NULL sizes
+ * it, otherwise out holds cap records and cap < *count is GOSSIP_EINVAL (nothing written). */
+int gossip_engine_get_launches(const gossip_engine* e, gossip_launch_record* out, uint32_t cap,
+                               uint32_t* count);
+/* Every k_pull instantiation the launch dispatch can select (kernel = GOSSIP_K_PULL, lpw, epn,
+ * flags; counts 0): nine lane shapes, two non-SP non-temporal kernels, sixteen SP kernels.  Sized
+ * and filled like gossip_engine_get_launches; needs no engine and no device. */
+int gossip_pull_instantiations(gossip_launch_record* out, uint32_t cap, uint32_t* count);
+
 /* First-contact trace (GOSSIP_F_TRACE): one record per (node, shareId) whose first
  * contact happened in a simulated tick; via_recv=1 for ReceiveShare, 0 for own
  * generation; hop = ticks since the winning source's generation. */

@@ -48,6 +48,7 @@
 
 #include "internal.h"
 #include "pull_plan.h"
+#include "launch_ledger.h"
 
 using gossip::set_error;
 using gossip::PullShape;
@@ -256,70 +257,79 @@ uint64_t pull_grid_cap(bool nt, int64_t ov) {
     return nt ? 16384ull : 4096ull;
 }
 
-// the flags k_pull<.., SP = true> takes as compile-time constants (pull_kernel.h): the same
-// conditions the kernel derives at run time.  Push marks (PullArgs::mark_*) run only there.
-bool pull_sp(int lpw, int epn, const PullArgs& a) {
-    return lpw == 32 && epn == 1 && a.tmask != nullptr && a.ptile != nullptr && a.sat != nullptr &&
+// What the SP instantiations k_pull<32, 1, .., SP = true> need beside their lane shape (pull_kernel.h):
+// the same conditions the kernel derives at run time.  Push marks (PullArgs::mark_*) run only there.
+bool pull_sp_ok(int lpw, const PullArgs& a) {
+    return a.tmask != nullptr && a.ptile != nullptr && a.sat != nullptr &&
            a.nptile / (uint32_t)(lpw / 8) <= kPullMaxPasses && !a.noskip && a.gate_seen;
+}
+bool pull_sp(int lpw, int epn, const PullArgs& a) { return lpw == 32 && epn == 1 && pull_sp_ok(lpw, a); }
+
+// One k_pull launch site: the key of the instantiation, from the template arguments, must be the
+// one the dispatch rule (launch_ledger.h, pull_dispatch) selected; 0: it is not, nothing launched.
+template <int LPW, int EPN, bool NT = false, bool SP = false, bool PUSH = false, bool SHORT = false, bool FOLD = false>
+uint32_t pull_go(uint32_t want, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    constexpr uint32_t key = gossip::pull_key(LPW, EPN, NT, SP, PUSH, SHORT, FOLD);
+    if (key != want) return 0u;
+    k_pull<LPW, EPN, NT, SP, PUSH, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+    return key;
 }
 
 // the SP instantiations: push marks, the batch schedule of exit-likely passes and folded rows each in
 // instantiations of their own (the plain one keeps its register allocation)
 template <int LPW, bool SHORT, bool FOLD>
-void launch_pull_sp(bool nt, bool push, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
-    if (nt && push)
-        k_pull<LPW, 1, true, true, true, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
-    else if (nt)
-        k_pull<LPW, 1, true, true, false, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
-    else if (push)
-        k_pull<LPW, 1, false, true, true, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
-    else
-        k_pull<LPW, 1, false, true, false, SHORT, FOLD><<<grid, 256, lds, s>>>(a);
+uint32_t launch_pull_sp(uint32_t want, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    const uint32_t f = gossip::pull_key_flags(want);
+    const bool nt = f & gossip::PK_NT, push = f & gossip::PK_PUSH;
+    if (nt && push) return pull_go<LPW, 1, true, true, true, SHORT, FOLD>(want, grid, lds, s, a);
+    if (nt) return pull_go<LPW, 1, true, true, false, SHORT, FOLD>(want, grid, lds, s, a);
+    if (push) return pull_go<LPW, 1, false, true, true, SHORT, FOLD>(want, grid, lds, s, a);
+    return pull_go<LPW, 1, false, true, false, SHORT, FOLD>(want, grid, lds, s, a);
 }
 template <int LPW, int EPN>
-void launch_pull_t(bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+uint32_t launch_pull_t(uint32_t want, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    const uint32_t f = gossip::pull_key_flags(want);
     if constexpr (LPW == 32 && EPN == 1) {
-        if (pull_sp(LPW, EPN, a)) {
-            const bool push = a.mark_cur != nullptr || a.mark_next != nullptr;
-            if (a.short_batch && a.fold)
-                launch_pull_sp<LPW, true, true>(nt, push, grid, lds, s, a);
-            else if (a.short_batch)
-                launch_pull_sp<LPW, true, false>(nt, push, grid, lds, s, a);
-            else if (a.fold)  // some tile of the launch is folded or read back (TM_FOLDW, TM_SEENF)
-                launch_pull_sp<LPW, false, true>(nt, push, grid, lds, s, a);
-            else
-                launch_pull_sp<LPW, false, false>(nt, push, grid, lds, s, a);
-            return;
+        if (f & gossip::PK_SP) {
+            const bool sb = f & gossip::PK_SHORT, fold = f & gossip::PK_FOLD;
+            if (sb && fold) return launch_pull_sp<LPW, true, true>(want, grid, lds, s, a);
+            if (sb) return launch_pull_sp<LPW, true, false>(want, grid, lds, s, a);
+            if (fold)  // some tile of the launch is folded or read back (TM_FOLDW, TM_SEENF)
+                return launch_pull_sp<LPW, false, true>(want, grid, lds, s, a);
+            return launch_pull_sp<LPW, false, false>(want, grid, lds, s, a);
         }
     }
     if constexpr ((LPW == 32 || LPW == 16) && EPN == 1) {
-        if (nt) {
-            k_pull<LPW, 1, true><<<grid, 256, lds, s>>>(a);
-            return;
-        }
+        if (f & gossip::PK_NT) return pull_go<LPW, 1, true>(want, grid, lds, s, a);
     }
-    if constexpr (LPW * EPN <= 64) k_pull<LPW, EPN><<<grid, 256, lds, s>>>(a);
+    if constexpr (LPW * EPN <= 64) return pull_go<LPW, EPN>(want, grid, lds, s, a);
+    return 0u;
 }
 
 template <int LPW>
-void launch_pull_e(int epn, bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
-    switch (epn) {
-        case 1: launch_pull_t<LPW, 1>(nt, grid, lds, s, a); break;
-        case 2: launch_pull_t<LPW, 2>(nt, grid, lds, s, a); break;
-        case 4: launch_pull_t<LPW, 4>(nt, grid, lds, s, a); break;
-        case 8: launch_pull_t<LPW, 8>(nt, grid, lds, s, a); break;
-        default: launch_pull_t<LPW, 8>(nt, grid, lds, s, a); break;
+uint32_t launch_pull_e(uint32_t want, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    switch (gossip::pull_key_epn(want)) {
+        case 1: return launch_pull_t<LPW, 1>(want, grid, lds, s, a);
+        case 2: return launch_pull_t<LPW, 2>(want, grid, lds, s, a);
+        case 4: return launch_pull_t<LPW, 4>(want, grid, lds, s, a);
+        case 8: return launch_pull_t<LPW, 8>(want, grid, lds, s, a);
+        default: return 0u;
     }
 }
 
 // The k_pull instantiation of a launch shape (pull_plan.h: lpw 8, 16 or 32, lpw * epn <= 64, both
-// powers of two).  False: no instantiation takes that lpw, nothing was launched.
-bool launch_pull(const PullShape& sh, bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
-    switch (sh.lpw) {  // lpw >= 8: one tile's 8 word-pairs sit in one lane group
-        case 8: launch_pull_e<8>(sh.epn, nt, grid, lds, s, a); return true;
-        case 16: launch_pull_e<16>(sh.epn, nt, grid, lds, s, a); return true;
-        case 32: launch_pull_e<32>(sh.epn, nt, grid, lds, s, a); return true;
-        default: return false;
+// powers of two): pull_dispatch (launch_ledger.h) names it, the switches below reach its launch
+// site, and the site checks that it is the one named.  Returns the key of the instantiation
+// launched; 0: no instantiation takes that shape, nothing was launched.
+uint32_t launch_pull(const PullShape& sh, bool nt, uint32_t grid, size_t lds, hipStream_t s, const PullArgs& a) {
+    const bool push = a.mark_cur != nullptr || a.mark_next != nullptr;
+    const uint32_t want = gossip::pull_dispatch(sh, nt, sh.lpw >= 8 && pull_sp_ok(sh.lpw, a), push,
+                                                a.short_batch != 0, a.fold != 0);
+    switch (gossip::pull_key_lpw(want)) {  // lpw >= 8: one tile's 8 word-pairs sit in one lane group
+        case 8: return launch_pull_e<8>(want, grid, lds, s, a);
+        case 16: return launch_pull_e<16>(want, grid, lds, s, a);
+        case 32: return launch_pull_e<32>(want, grid, lds, s, a);
+        default: return 0u;
     }
 }
 
@@ -908,6 +918,8 @@ struct gossip_engine {
     std::vector<double> hop_front;         // expected frontier fraction per hop (BFS layer model)
     uint32_t last_lpw = 0, last_dense_tiles = 0;
     uint64_t sat_launches = 0;
+    // launches by (kernel, variant) since creation (launch_ledger.h; gossip_engine_get_launches)
+    gossip::LaunchLedger ledger;
     bool dense_row_hop(uint32_t tl, int64_t hop) const;
     void mark_inject(uint32_t tl, int64_t t) {
         if (tile_last_inject[tl] != t) {
@@ -2497,8 +2509,11 @@ int gossip_engine::run_pull(const TickPlan& p, const PullArgs& base) {
         }
         last_lpw = (uint32_t)win.shape.lpw;
         const size_t lds = pull_lds_bytes(c.wact, c.keep_lds != 0, c.nptile) + extra_lds;
-        if (!launch_pull(win.shape, p.nt_rows, grid, lds, stream, c))
-            return set_error(GOSSIP_EHIP, "k_pull: no instantiation for " + std::to_string(win.shape.lpw) + " word-lanes");
+        const uint32_t key = launch_pull(win.shape, p.nt_rows, grid, lds, stream, c);
+        if (!key)
+            return set_error(GOSSIP_EHIP, "k_pull: no instantiation for " + std::to_string(win.shape.lpw) + " x " +
+                                              std::to_string(win.shape.epn) + " lanes");
+        ledger.add(gossip::LK_PULL, key, gossip::launch_strides((uint64_t)grid * 4u, ((uint64_t)base.n - base.v0 + 63u) / 64u));
     }
     return GOSSIP_OK;
 }
@@ -2549,12 +2564,18 @@ int gossip_engine::launch_young(const TickPlan& p, const PullArgs& a, hipStream_
     last_young_grid = yg;
     if (y.fast) {  // the idle nodes first (young_kernel.h, k_young_idle)
         const uint64_t nch = ((uint64_t)(v1 - v0) + 63) / 64;
-        k_young_idle<<<(uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nch + 3) / 4, 16384)), 256, 0, ys>>>(y);
+        const uint32_t ig = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nch + 3) / 4, 16384));
+        k_young_idle<<<ig, 256, 0, ys>>>(y);
+        ledger.add(gossip::LK_YOUNG_IDLE, 0u, gossip::launch_strides((uint64_t)ig * 4u, nch));
     }
-    if (y.sparse_rd || y.fast || !p.ny_read)
+    const bool ystrides = gossip::launch_strides((uint64_t)yg * 4u, ((uint64_t)(v1 - v0) + 63) / 64);
+    if (y.sparse_rd || y.fast || !p.ny_read) {
         k_pull_young<true><<<yg, 256, young_lds_bytes(p.ny, p.ny_read), ys>>>(y);
-    else
+        ledger.add(gossip::LK_PULL_YOUNG, 1u, ystrides);
+    } else {
         k_pull_young<false><<<yg, 256, young_lds_bytes(p.ny, p.ny_read), ys>>>(y);
+        ledger.add(gossip::LK_PULL_YOUNG, 0u, ystrides);
+    }
     HIP_TRY(hipGetLastError());
     if (cfg.flags & GOSSIP_F_TIMING) {
         HIP_TRY(hipEventRecord(y1, ys));
@@ -2575,6 +2596,7 @@ void gossip_engine::run_dedup(const PullArgs& base) {
         c.wbase = wb;
         c.wact = std::min(kPullLdsWords, hw - wb);
         k_dense_dedup<<<g, 64 * kDedupWaves, pull_lds_bytes(c.wact, c.keep_lds != 0), stream>>>(c);
+        ledger.add(gossip::LK_DENSE_DEDUP, 0u, gossip::launch_strides((uint64_t)g * kDedupWaves, rows));
     }
 }
 
@@ -2593,6 +2615,7 @@ int gossip_engine::run_dense(uint64_t lo, uint64_t hi, const unsigned long long*
     gm.ksplit = ks;
     gm.total = gm.mb * gm.nt * ks;
     k_dense_bits<<<(gm.total + 7u) / 8u * 8u, 512, 0, stream>>>(gm);
+    ledger.add(gossip::LK_DENSE_BITS, gm.ksplit, gossip::dense_split_uneven(nst, gm.ksplit));
     HIP_TRY(hipGetLastError());
     return GOSSIP_OK;
 }
@@ -4650,6 +4673,44 @@ int gossip_engine_reset_timing(gossip_engine* e) {
         HIP_TRY(hipMemsetAsync(e->d_acct, 0, kAcctSlots * kAcctReplicas * 8, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
+    return GOSSIP_OK;
+}
+
+// a ledger record (launch_ledger.h) in the ABI's form
+static gossip_launch_record launch_record_of(const gossip::LaunchRecord& r) {
+    gossip_launch_record o;
+    std::memset(&o, 0, sizeof(o));
+    o.kernel = r.kernel;
+    if (r.kernel == gossip::LK_PULL) {
+        o.lpw = gossip::pull_key_lpw(r.variant);
+        o.epn = gossip::pull_key_epn(r.variant);
+        o.flags = gossip::pull_key_flags(r.variant);
+    } else {
+        o.arg = r.variant;
+    }
+    o.launches = r.launches;
+    o.strided = r.strided;
+    return o;
+}
+
+int gossip_engine_get_launches(const gossip_engine* e, gossip_launch_record* out, uint32_t cap, uint32_t* count) {
+    if (!e || !count) return set_error(GOSSIP_EINVAL, "NULL argument");
+    const std::vector<gossip::LaunchRecord>& recs = e->ledger.records();
+    *count = (uint32_t)recs.size();
+    if (!out) return GOSSIP_OK;
+    if (cap < recs.size()) return set_error(GOSSIP_EINVAL, "get_launches: " + std::to_string(recs.size()) + " records, room for " + std::to_string(cap));
+    for (size_t i = 0; i < recs.size(); i++) out[i] = launch_record_of(recs[i]);
+    return GOSSIP_OK;
+}
+
+int gossip_pull_instantiations(gossip_launch_record* out, uint32_t cap, uint32_t* count) {
+    if (!count) return set_error(GOSSIP_EINVAL, "NULL argument");
+    *count = gossip::kPullInstantiations;
+    if (!out) return GOSSIP_OK;
+    if (cap < gossip::kPullInstantiations) return set_error(GOSSIP_EINVAL, "pull_instantiations: room for " + std::to_string(cap) + " of 27 records");
+    const uint32_t* k = gossip::pull_instantiations();
+    for (uint32_t i = 0; i < gossip::kPullInstantiations; i++)
+        out[i] = launch_record_of(gossip::LaunchRecord{gossip::LK_PULL, k[i], 0u, 0u});
     return GOSSIP_OK;
 }
 

@@ -60,8 +60,12 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_exchange_export_chunk", "gossip_engine_exchange_import_chunk",
     "gossip_format_netanim", "gossip_topology_load_links", "gossip_schedule_load_events",
     "gossip_engine_abort", "gossip_engine_get_rehearsal", "gossip_engine_get_rehearsal_peak",
-    "gossip_engine_get_option",
+    "gossip_engine_get_option", "gossip_engine_get_launches", "gossip_pull_instantiations",
 )
+
+# launch ledger (gossip.h): kernel ids and k_pull's template flags
+K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP = range(5)
+PULL_NT, PULL_SP, PULL_PUSH, PULL_SHORT, PULL_FOLD = 1, 2, 4, 8, 16
 
 # NS-3 5 Mbps point-to-point links (p2pnetwork.cc:113): ns per byte, PPP+IPv4+TCP(timestamp
 # option) header bytes, TcpSocketBase's one-TimeStep send deferral (gossip.h)
@@ -121,6 +125,43 @@ class gossip_counters(C.Structure):
     ]
 
 
+class gossip_launch_record(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_uint32), ("lpw", C.c_uint32), ("epn", C.c_uint32), ("flags", C.c_uint32),
+        ("arg", C.c_uint32), ("pad0", C.c_uint32), ("launches", C.c_uint64), ("strided", C.c_uint64),
+    ]
+
+
+@dataclass(frozen=True)
+class Launch:
+    """One record of the launch ledger (gossip.h, gossip_launch_record)."""
+    kernel: int
+    lpw: int
+    epn: int
+    flags: int
+    arg: int
+    launches: int
+    strided: int
+
+    @property
+    def key(self):
+        """(kernel, lpw, epn, flags, arg): the variant, without its counts."""
+        return (self.kernel, self.lpw, self.epn, self.flags, self.arg)
+
+
+def _launch_records(call, what: str):
+    cnt = C.c_uint32(0)
+    _check(call(None, 0, C.byref(cnt)), what)
+    arr = (gossip_launch_record * max(1, cnt.value))()
+    _check(call(arr, cnt.value, C.byref(cnt)), what)
+    return [Launch(r.kernel, r.lpw, r.epn, r.flags, r.arg, r.launches, r.strided) for r in arr[:cnt.value]]
+
+
+def pull_instantiations():
+    """Every k_pull instantiation the launch dispatch can select, as Launch records with zero counts."""
+    return _launch_records(load_library().gossip_pull_instantiations, "pull instantiations")
+
+
 _lib = None
 
 
@@ -150,6 +191,8 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_get_rehearsal": (C.c_int, [P, u32, P, P, P, P, C.POINTER(u64)]),
         "gossip_engine_get_rehearsal_peak": (C.c_int, [P, u32, P]),
         "gossip_engine_get_option": (C.c_int, [P, C.c_char_p, C.POINTER(i64)]),
+        "gossip_engine_get_launches": (C.c_int, [P, C.POINTER(gossip_launch_record), u32, C.POINTER(u32)]),
+        "gossip_pull_instantiations": (C.c_int, [C.POINTER(gossip_launch_record), u32, C.POINTER(u32)]),
         "gossip_topology_num_nodes": (u32, [P]),
         "gossip_topology_num_links": (u64, [P]),
         "gossip_topology_get_links": (C.c_int, [P, P, P]),
@@ -556,6 +599,11 @@ class Engine:
 
     def reset_timing(self):
         _check(load_library().gossip_engine_reset_timing(self._h), "reset timing")
+
+    def launches(self):
+        """The launch ledger: Launch records by (kernel, variant), cumulative since creation."""
+        lib = load_library()
+        return _launch_records(lambda out, cap, cnt: lib.gossip_engine_get_launches(self._h, out, cap, cnt), "launches")
 
     def rehearsal(self, ranges: int) -> dict:
         """Option rehearse_rows = ranges: per row block, summed since reset_timing -- pull, pack

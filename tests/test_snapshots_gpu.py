@@ -74,7 +74,7 @@ def _run(gossip, name, lat, ts, **kw):
     try:
         eng.run()
         eng.sync()
-        return eng.stats(), eng.counters(), [eng.snapshot(k) for k in range(len(ts))]
+        return eng.stats(), TS.counters_with_ledger(eng), [eng.snapshot(k) for k in range(len(ts))]
     finally:
         eng.close()
 

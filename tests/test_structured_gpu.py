@@ -20,6 +20,9 @@ pytestmark = pytest.mark.gpu
 
 STATS = ("gen", "recv", "fwd", "sent", "processed", "peers", "sockets")
 TPT = "F_TILE_PER_TICK"
+# the launch ledger's kernel ids and k_pull template flags (include/gossip.h)
+K_PULL, K_PULL_YOUNG = 0, 1
+PULL_NT, PULL_SP, PULL_PUSH = 1, 2, 4
 
 # CSR paths: (flag names, options)
 PATHS = {
@@ -55,6 +58,13 @@ def _topo(gossip, name):
     return _topos[name]
 
 
+def counters_with_ledger(eng):
+    """The engine's counters with its launch ledger riding along as .launches (what _ran reads)."""
+    c = eng.counters()
+    c.launches = eng.launches()
+    return c
+
+
 def _engine_run(gossip, name, flags=(), opts=(), lat=L, mode=None, graph="topology", probe=None):
     """One engine over the family's inputs: (stats, counters, trace); with probe = k the run stops after
     k ticks and reads the counters there as well (the "last tick" counters while floods still run)."""
@@ -77,14 +87,18 @@ def _engine_run(gossip, name, flags=(), opts=(), lat=L, mode=None, graph="topolo
             mid = eng.counters()
         eng.run()
         eng.sync()
-        out = eng.stats(), eng.counters(), eng.trace()
+        out = eng.stats(), counters_with_ledger(eng), eng.trace()
         return out if probe is None else out + (mid,)
     finally:
         eng.close()
 
 
 def _assert_parity(oracle, name, lat, st, tr, what):
-    f = _family(name)
+    assert_parity_inputs(oracle, _family(name), lat, st, tr, what)
+
+
+def assert_parity_inputs(oracle, f, lat, st, tr, what):
+    """The engine's counters and first-contact trace against ORACLE A on the inputs f (n, a, b, ev, t_cut)."""
     r = oracle.run_replay(f["n"], lat, T0, f["t_cut"], f["a"], f["b"], f["ev"]["ns"], f["ev"]["node"],
                           f["ev"]["share_id"], trace=True)
     for k in STATS:
@@ -129,6 +143,21 @@ def _ran(path, c, name):
         assert c.young_skip_ticks > 0, what
     else:
         assert path.startswith("young") or c.young_launches == 0, what
+    # ... and in the launch ledger: the k_pull instantiations that ran, from their launch sites
+    pulls = [r for r in c.launches if r.kernel == K_PULL]
+    assert pulls and sum(r.launches for r in pulls) >= c.pull_launches, what  # (pull_launches: since reset)
+    sp = [r for r in pulls if r.flags & PULL_SP]
+    assert all((r.lpw, r.epn) == (32, 1) for r in sp), what
+    if path in ("default", "wide", "dense_rows", "dense_rows_nosat"):
+        assert not any(r.flags & PULL_NT for r in pulls), what
+    if path in ("wide_nt_push", "push_off"):  # pull_nt 1: every kernel that has a non-temporal form ran it
+        assert all(r.flags & PULL_NT for r in pulls if r.epn == 1 and r.lpw >= 16), what
+    if path == "push_off":  # "the non-PUSH SP kernel": an SP instantiation ran, and none with push marks
+        assert sp and not any(r.flags & PULL_PUSH for r in pulls), what
+    if path in ("no_tile_lists", "noskip", "dense_rows_nosat"):  # no saturation words: no SP instantiation
+        assert not sp, what
+    young = [r for r in c.launches if r.kernel == K_PULL_YOUNG]
+    assert sum(r.launches for r in young) >= c.young_launches and bool(young) == path.startswith("young"), what
 
 
 def _ran_ladder(path, c, name, dense_tiles=None):
