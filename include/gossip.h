@@ -192,6 +192,12 @@ typedef struct gossip_config {
                                        births of a tick fill whole tiles of one age
                                        (gossip_shard_events_by_tick; every engine of a job must
                                        use the same rule)                                        */
+#define GOSSIP_F_REACH 512u /* reach profiles: every tick a kernel (k_reach) counts the tick's first
+                               contacts per share column on the GPU, and the host bins them by
+                               (generation event, hop) -- gossip_engine_get_reach / _get_reach_totals
+                               below.  Off by default; with the flag off nothing is launched.
+                               GOSSIP_REACH=1 in the environment sets it for every engine created
+                               (profiling an unchanged driver).                                   */
 
 int gossip_engine_create(const gossip_config* cfg, gossip_engine** out);
 /* Graph: CSR over distinct neighbours with multiplicity in {1,2} (see topology above).  The CSR
@@ -351,6 +357,15 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  *                      folded, "pull_sat" 0 and "pull_tiles" 0 are refused (GOSSIP_EINVAL): the seen
  *                      rows of its saturated nodes are stale behind their saturation bits
  *                                                                          [GOSSIP_SEEN_FOLD]
+ *   "reach_hops"       reach profiles (GOSSIP_F_REACH): hop bins per share, 2..1024 (32); the last
+ *                      bin collects every hop >= reach_hops - 1 (before the schedule)
+ *                                                                          [GOSSIP_REACH_HOPS]
+ *   "reach_shares"     reach profiles: 1 keeps the per-event table on the host, 4 x reach_hops bytes
+ *                      per event (default), 0 only the totals by hop (before the schedule)
+ *                                                                          [GOSSIP_REACH_SHARES]
+ *   "reach_flush"      reach profiles, tests: rows a lane of k_reach adds to its bit planes between
+ *                      flushes, 1..255 (255, the planes' capacity): small values make small graphs
+ *                      cross flush boundaries                              [GOSSIP_REACH_FLUSH]
  *   "xchunks"          row partition: row chunks per tick of the pipelined exchange, 1..16 (4);
  *                      equal on every rank of a partition                    [GOSSIP_XCHUNKS]
  *   "rehearse_rows"    diagnostic, R >= 2 on an unpartitioned CSR engine (before the schedule;
@@ -457,6 +472,13 @@ typedef struct gossip_counters {
     uint64_t young_idle_ticks;   /* k_pull_young launches that skipped their idle nodes' walks (young_idle) */
     uint64_t pull_fold_rows;     /* tile rows k_pull wrote folded -- seen | new in the F_next row, no seen
                                     write -- since reset (option seen_fold) */
+    /* reach profiles (GOSSIP_F_REACH) */
+    uint64_t reach_launches;     /* ticks whose first contacts were counted (a tick with an empty window
+                                    launches no kernel and is counted), since creation */
+    double reach_ms;             /* summed HIP-event time of k_reach + k_reach_slots (TIMING), since reset */
+    uint64_t reach_bytes;        /* bytes those kernels loaded: frontier, mask, occupancy and slot reads,
+                                    since reset */
+    double reach_slots_ms;       /* of reach_ms, the part of k_reach_slots (TIMING), since reset */
 } gossip_counters;
 int gossip_engine_get_counters(gossip_engine* e, gossip_counters* c);
 /* Option rehearse_rows = R: per row block r < R, summed since the last reset_timing -- pull time,
@@ -476,7 +498,12 @@ int gossip_engine_reset_timing(gossip_engine* e);
  *   lpw, epn  k_pull: word-lanes and edge-lanes per node (0 for the other kernels)
  *   flags     k_pull: GOSSIP_PULL_* template flags (0 for the other kernels)
  *   arg       k_pull_young: its template argument (1: the sparse-tick instantiation);
- *             k_dense_bits: the K split (ksplit); 0 otherwise
+ *             k_dense_bits: the K split (ksplit); GOSSIP_K_REACH: 16 | modes for k_reach (dense
+ *             rows), modes = the union of its tiles' modes in that launch: 1 rows behind occupancy
+ *             bits, 2 write-sparse tiles (overflowed nodes' rows), 4 folded rows masked with the
+ *             other frontier buffer, 8 folded rows masked with seen rows; 1 k_reach_slots with every
+ *             counter in LDS, 2 k_reach_slots with more than 8 write-sparse tiles (the 8 oldest
+ *             tiles' counters in LDS, a global atomic per entry of the others); 0 otherwise
  *   launches  launches of that variant
  *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's
  *             grid-stride loop ran more than once: k_pull, k_pull_young and k_young_idle 4 x blocks <
@@ -489,6 +516,7 @@ int gossip_engine_reset_timing(gossip_engine* e);
 #define GOSSIP_K_YOUNG_IDLE 2
 #define GOSSIP_K_DENSE_BITS 3
 #define GOSSIP_K_DENSE_DEDUP 4
+#define GOSSIP_K_REACH 5      /* k_reach / k_reach_slots (GOSSIP_F_REACH only) */
 #define GOSSIP_PULL_NT 1u     /* non-temporal row accesses                  */
 #define GOSSIP_PULL_SP 2u     /* tile masks, saturation bits (32 x 1 lanes) */
 #define GOSSIP_PULL_PUSH 4u   /* push marks                                 */
@@ -519,6 +547,30 @@ int gossip_pull_instantiations(gossip_launch_record* out, uint32_t cap, uint32_t
 uint64_t gossip_engine_trace_size(const gossip_engine* e);
 int gossip_engine_get_trace(const gossip_engine* e, uint32_t* node, uint32_t* share_id,
                             int64_t* tick, uint32_t* hop, uint8_t* via_recv);
+
+/* Reach profiles (GOSSIP_F_REACH): reach[k][h] = the number of nodes whose first contact with
+ * event k's share came from k's column at hop h (ticks since k's generation; hop 0 = the own
+ * generation), h < hops = option "reach_hops", the last bin collecting every later hop.  They
+ * replace histogramming a first-contact trace (GOSSIP_F_TRACE, which stops the stream every tick and
+ * walks the frontier on the host: small runs only): with both flags set, reach[k][h] summed over the
+ * events k of one share_id equals the number of trace records with that (share_id, hop), the lost
+ * generations of the handshake window (hop 0 only) included.  Events that never get a column -- a
+ * generation at a node without peers, or of an id its node has already processed -- have all-zero
+ * rows.  Event indices are those of the array given to gossip_engine_set_schedule (for
+ * _set_schedule_obj: the order of gossip_schedule_get).
+ *   Cost: one memory-bound kernel pass per tick over the occupied 128-B rows the tick wrote, a
+ * 256 B x live-words copy to the host per tick through a ring of pinned buffers (no stream
+ * synchronisation per tick), and on the host 4 x hops bytes per event ("reach_shares" 1) or 8 x hops
+ * bytes in all ("reach_shares" 0).  Both calls wait for the stream and fold in what is pending.
+ *   A row-partition rank counts its own rows only, and a share shard's table is zero for the events
+ * it does not own: sum the tables (and totals) over ranks and over shards.
+ *   gossip_engine_get_reach_totals: by_hop[h] = sum over events; *hops = the bin count (either may
+ * be NULL); cap_hops < the bin count with by_hop set is GOSSIP_EINVAL.
+ *   gossip_engine_get_reach: rows [first_event, first_event + num_events) into out (num_events x
+ * hops, row-major); a range past the schedule is GOSSIP_EINVAL, "reach_shares" 0 GOSSIP_ESTATE.
+ * Both return GOSSIP_ESTATE without the flag or before the schedule. */
+int gossip_engine_get_reach_totals(gossip_engine* e, uint32_t cap_hops, uint64_t* by_hop, uint32_t* hops);
+int gossip_engine_get_reach(gossip_engine* e, uint64_t first_event, uint64_t num_events, uint32_t* out);
 
 void gossip_engine_destroy(gossip_engine* e);
 

@@ -49,6 +49,7 @@
 #include "internal.h"
 #include "pull_plan.h"
 #include "launch_ledger.h"
+#include "reach_kernel.h"
 
 using gossip::set_error;
 using gossip::PullShape;
@@ -877,7 +878,7 @@ struct gossip_engine {
     std::vector<int64_t> tile_foldw;       // last tick k_pull wrote the tile's rows folded (TM_FOLDW)
     std::vector<uint8_t> tile_folded;      // the tile was folded in this life: saturated nodes' seen rows are stale
     bool fold_barred = false;              // a tick dropped receptions by a keep mask: peers' old bits are no longer safe
-    std::vector<uint8_t> tr_foldw, tr_seenf;  // per tile: this tick's TM_FOLDW / TM_SEENF (decode_trace)
+    std::vector<uint8_t> tr_foldw, tr_seenf;  // per tile: this tick's TM_FOLDW / TM_SEENF (decode_trace, k_reach)
     bool any_folded() const {
         for (size_t tl = 0; tl < tile_folded.size() && tl < tile_alloc.size(); tl++)
             if (tile_alloc[tl] && tile_folded[tl]) return true;
@@ -978,6 +979,45 @@ struct gossip_engine {
         uint8_t via;
     };
     std::vector<Tr> tr;
+    // ---- reach profiles (GOSSIP_F_REACH; reach_kernel.h): per tick, k_reach counts the tick's first
+    // contacts per column into d_rcnt[t % kRing]; the counts come back through h_rcnt like the
+    // liveness words and the host folds them into (event, hop) bins with col_src -- no later than
+    // the retirement pass that reads the same tick's liveness, so a column still names the event
+    // that produced its count
+    bool reach = false;
+    int64_t opt_reach_hops = 32;    // bins per share; the last collects every hop >= H - 1
+    int64_t opt_reach_shares = 1;   // 1: the per-event table (4 H bytes per event), 0: totals by hop only
+    int64_t opt_reach_flush = gossip::kReachCap;  // rows a lane adds between plane flushes (tests)
+    std::vector<uint32_t> reach_tab;   // ev.size() x H (this engine's events, its own rows)
+    std::vector<uint64_t> reach_tot;   // H
+    std::vector<uint32_t> reach_of;    // caller's event index -> index in ev (UINT32_MAX: no column ever)
+    uint32_t* d_rcnt[kRing] = {};
+    uint32_t* h_rcnt[kRing] = {};
+    uint32_t* d_rtile[kRing] = {};
+    uint32_t* h_rtile[kRing] = {};
+    hipEvent_t reach_done[kRing] = {};
+    bool reach_pending[kRing] = {};
+    int64_t reach_tick[kRing] = {};
+    uint32_t reach_hw[kRing] = {};
+    uint32_t reach_cap = 0;            // words the ring buffers hold
+    unsigned long long* d_rbytes = nullptr;
+    uint64_t reach_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_reach;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_reach_slots;  // (second events shared with timers_reach)
+    double reach_ms_done = 0.0, reach_slots_ms_done = 0.0;
+    std::vector<uint8_t> reach_ws;      // per tile: write-sparse this tick (reach_launch's scratch)
+    uint64_t reach_ring_bytes(uint32_t words) const;
+    int reach_alloc();
+    int reach_launch(int64_t t);        // tick_step_b: the tick's counts, read back asynchronously
+    int reach_fold_slot(int ls);        // one pending tick into the bins
+    int reach_fold_upto(int64_t kt);    // every pending tick <= kt, in tick order
+    int reach_drain();                  // wait for the stream, fold everything pending
+    void reach_add(uint32_t src, int64_t hop, uint32_t c) {
+        const int64_t H = opt_reach_hops;
+        const size_t h = (size_t)std::min<int64_t>(hop, H - 1);
+        reach_tot[h] += c;
+        if (opt_reach_shares) reach_tab[(size_t)src * (size_t)H + h] += c;
+    }
 
     ~gossip_engine();
     int alloc_device();
@@ -1108,6 +1148,12 @@ gossip_engine::~gossip_engine() {
         hipEventDestroy(p.first);
         hipEventDestroy(p.second);
     }
+    for (auto& p : timers_reach) {
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    for (auto& p : timers_reach_slots) hipEventDestroy(p.first);
+    hipFree(d_rbytes);
     if (comm && !aborted.load()) ncclCommDestroy(comm);  // (an aborted communicator is already freed)
     for (int k = 0; k < kRing; k++) {
         hipFree(d_ctl[k]); hipFree(d_births[k]); hipFree(d_gphase[k]); hipFree(d_wflags[k]);
@@ -1116,6 +1162,8 @@ gossip_engine::~gossip_engine() {
         hipHostFree(h_live[k]);
         if (slot_done[k]) hipEventDestroy(slot_done[k]);
         if (live_done[k]) hipEventDestroy(live_done[k]);
+        hipFree(d_rcnt[k]); hipHostFree(h_rcnt[k]); hipFree(d_rtile[k]); hipHostFree(h_rtile[k]);
+        if (reach_done[k]) hipEventDestroy(reach_done[k]);
     }
     for (auto& p : timers_phase) {
         hipEventDestroy(p.first);
@@ -1443,7 +1491,8 @@ int gossip_engine::alloc_device() {
         const uint64_t want = stride + std::max<uint64_t>(stride / 4, 2 * kTileWords);
         const uint64_t other = (uint64_t)n * 24 + nnz * 4 + ((uint64_t)n + 1) * 8 + slot_bytes +
                                24ull * n * ((want + 1023u) / 1024u) + (4ull << 30);  // + RCCL / context (24: nz x 2 + sat)
-        const uint64_t per_word = 3ull * n * 8 + (dense ? 16ull * n_pad : 0ull);  // (DENSE: FT x 2)
+        const uint64_t per_word = 3ull * n * 8 + (dense ? 16ull * n_pad : 0ull) +  // (DENSE: FT x 2)
+                                  (reach ? (uint64_t)kRing * 257u : 0ull);         // (reach: the count ring)
         uint64_t fit = freeb > other ? ((uint64_t)freeb - other) / per_word : 0ull;
         fit = fit / kTileWords * kTileWords;
         stride = (uint32_t)std::max<uint64_t>(stride, std::min<uint64_t>(want / kTileWords * kTileWords, fit));
@@ -1463,7 +1512,7 @@ int gossip_engine::alloc_device() {
     const uint64_t bm_seen = (uint64_t)seen_n * stride * 8;
     const uint64_t need = 2 * bm + bm_seen + (uint64_t)n * 24 + (nnz * 4) + ((uint64_t)n + 1) * 8 + slot_bytes +
                           24ull * n * ((stride + 1023u) / 1024u) +
-                          (dense ? (uint64_t)stride * 8 * n_pad : 0ull);
+                          (dense ? (uint64_t)stride * 8 * n_pad : 0ull) + reach_ring_bytes(stride);
     if (need > (uint64_t)freeb)
         return set_error(GOSSIP_ENOMEM, "device memory: need " + std::to_string(need) +
                                             " bytes for a " + std::to_string(stride) +
@@ -1615,6 +1664,8 @@ int gossip_engine::alloc_device() {
     word_insts.assign(stride, {});
     col_phase.assign((size_t)stride * 64, 0);
     col_src.assign((size_t)stride * 64, UINT32_MAX);
+    if (reach)  // (its bytes are in `need` above)
+        if (int rc = reach_alloc()) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
     return GOSSIP_OK;
 }
@@ -1627,7 +1678,9 @@ int gossip_engine::grow(uint32_t new_stride) {
     size_t freeb = 0, totalb = 0;
     HIP_TRY(hipMemGetInfo(&freeb, &totalb));
     int ok = nb + (64ull << 20) <= (uint64_t)freeb ? 1 : 0;
-    if (opt_mem_limit > 0 && device_bytes + 3 * (nb - (uint64_t)n * stride * 8) > (uint64_t)opt_mem_limit) ok = 0;
+    if (opt_mem_limit > 0 && device_bytes + 3 * (nb - (uint64_t)n * stride * 8) + reach_ring_bytes(new_stride) -
+                                     reach_ring_bytes(stride) > (uint64_t)opt_mem_limit)
+        ok = 0;
     if (comm) {
         // Row-partitioned ranks widen in lockstep (their strides must agree for the exchange):
         // all of them grow or all fail, never one rank alone while the others wait in the next
@@ -1780,6 +1833,7 @@ int gossip_engine::grow(uint32_t new_stride) {
     device_bytes += (2ull * n + seen_n) * (uint64_t)(new_stride - stride) * 8;
     stride = new_stride;
     grows++;
+    if (reach) return reach_alloc();  // the count ring follows the window (pending ticks folded first)
     return GOSSIP_OK;
 }
 
@@ -1889,6 +1943,8 @@ int gossip_engine::retire_early(int64_t t) {
     HIP_TRY(hipEventSynchronize(live_done[ls]));
     live_pending[ls] = false;  // (consumed: the regular step of tick t + 1 has nothing left to read)
     early_retires++;
+    if (reach)  // the counts of every tick up to kt name their events through col_src: fold them first
+        if (int rc = reach_fold_upto(kt)) return rc;
     return retire_from(kt, h_live[ls]);
 }
 
@@ -1938,6 +1994,8 @@ int gossip_engine::stage_births(TickPlan& p) {
     {
         const int64_t kt = t - kLag;
         const int ls = (int)(((kt % kRing) + kRing) % kRing);
+        if (reach)  // (reach profiles: before the retirement below clears a column's source)
+            if (int rc = reach_fold_upto(kt)) return rc;
         if (kt >= tick0 && live_pending[ls] && live_tick[ls] == kt) {
             HIP_TRY(hipEventSynchronize(live_done[ls]));
             live_pending[ls] = false;
@@ -1968,6 +2026,7 @@ int gossip_engine::stage_births(TickPlan& p) {
             b.kind = BIRTH_LOST;
             I.state = 2;
             if (trace) tr.push_back(Tr{e.node, e.share_id, t, 0u, (uint8_t)0});
+            if (reach && e.node >= v0 && e.node < v1) reach_add((uint32_t)q, 0, 1u);  // (no column: its hop-0 bin)
         } else if (I.state == 2) {
             b.kind = BIRTH_NOOP;
         } else {
@@ -2308,7 +2367,7 @@ int gossip_engine::build_tile_masks(TickPlan& p) {
     if (p.keep_any) fold_barred = true;
     const bool fold_ok = opt_seen_fold != 0 && p.sat_used && p.dr_used && !fold_barred && !handshake && !batch &&
                          !link_timing && opt_rehearse_rows <= 1;
-    if (trace) {
+    if (trace || reach) {
         tr_foldw.assign(hw / kTileWords, 0);
         tr_seenf.assign(hw / kTileWords, 0);
     }
@@ -2372,7 +2431,7 @@ int gossip_engine::build_tile_masks(TickPlan& p) {
             }
             if (seenf || foldw) {
                 win.fold = true;
-                if (trace) {
+                if (trace || reach) {
                     tr_foldw[tl] = foldw;
                     tr_seenf[tl] = seenf;
                 }
@@ -3471,6 +3530,10 @@ int gossip_engine::tick_step_b(int64_t t) {
         HIP_TRY(hipEventRecord(ev_xdone, xstream));
         HIP_TRY(hipStreamWaitEvent(stream, ev_xdone, 0));
     }
+    if (reach) {  // the tick's first contacts per column (before the flip: d_F[nxt] is what the tick wrote)
+        int rc = reach_launch(t);
+        if (rc) return rc;
+    }
     // 6. liveness read-back (consumed kLag ticks later)
     {
         const int ls = (int)(t % kRing);
@@ -3496,6 +3559,166 @@ int gossip_engine::tick_step_b(int64_t t) {
         if (rc) return rc;
     }
     return GOSSIP_OK;
+}
+
+// ---- reach profiles (GOSSIP_F_REACH; reach_kernel.h) --------------------------------------
+// The tick's counts: k_reach over the allocated tiles of the window (dense rows, by decode_trace's
+// rules for where the tick's new bits live) and k_reach_slots over the write-sparse tiles' slot
+// entries, into d_rcnt[t % kRing]; then an asynchronous copy to h_rcnt and an event, like the
+// liveness words.  Runs before tick_step_b flips fcur: d_F[fcur ^ 1] is what the tick wrote,
+// d_F[fcur] and the seen rows are what it read (the next tick's launches come after these).
+// device bytes of the count ring at a window of `words`: per slot the counts (256 B per word) and
+// the tile list (one entry per tile + the write-sparse list), plus the byte tally
+uint64_t gossip_engine::reach_ring_bytes(uint32_t words) const {
+    return reach ? (uint64_t)kRing * ((uint64_t)words * 256u + ((uint64_t)words / kTileWords + 64u) * 4u) + 8u : 0ull;
+}
+
+// (Re)allocate the count ring for the current window capacity: alloc_device and grow.  What is
+// pending in the old ring is folded first.
+int gossip_engine::reach_alloc() {
+    if (int rc = reach_drain()) return rc;
+    const size_t cols = (size_t)stride * 64, tcap = stride / kTileWords + 64;
+    for (int k = 0; k < kRing; k++) {
+        hipFree(d_rcnt[k]); hipHostFree(h_rcnt[k]); hipFree(d_rtile[k]); hipHostFree(h_rtile[k]);
+        d_rcnt[k] = h_rcnt[k] = d_rtile[k] = h_rtile[k] = nullptr;
+        HIP_TRY(hipMalloc(&d_rcnt[k], cols * 4));
+        HIP_TRY(hipHostMalloc(&h_rcnt[k], cols * 4, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(&d_rtile[k], tcap * 4));
+        HIP_TRY(hipHostMalloc(&h_rtile[k], tcap * 4, hipHostMallocDefault));
+        if (!reach_done[k]) HIP_TRY(hipEventCreateWithFlags(&reach_done[k], hipEventDisableTiming));
+    }
+    if (!d_rbytes) {
+        HIP_TRY(hipMalloc(&d_rbytes, 8));
+        HIP_TRY(hipMemsetAsync(d_rbytes, 0, 8, stream));
+    }
+    device_bytes += reach_ring_bytes(stride) - (reach_cap ? reach_ring_bytes(reach_cap) : 0ull);
+    reach_cap = stride;
+    return GOSSIP_OK;
+}
+
+int gossip_engine::reach_launch(int64_t t) {
+    const int ls = (int)(((t % kRing) + kRing) % kRing);
+    reach_launches++;
+    if (reach_pending[ls])  // (folded two ticks ago by stage_births; never later than here)
+        if (int rc = reach_fold_upto(reach_tick[ls])) return rc;
+    if (!hw) return GOSSIP_OK;
+    const int nxt = fcur ^ 1;
+    // the block columns: every allocated tile with its mode (a retired tile's rows hold nothing
+    // that has a source), then the write-sparse index -> tile list of k_reach_slots
+    uint32_t* T = h_rtile[ls];
+    uint32_t nt = 0, modes = 0;
+    const uint32_t ntiles = hw / kTileWords;
+    const uint32_t nwt = young ? (uint32_t)wt_last.size() : 0u;
+    std::vector<uint8_t>& ws_tile = reach_ws;  // (kept between ticks: no allocation on the launch path)
+    ws_tile.assign(ntiles, 0);
+    for (uint32_t q = 0; q < nwt; q++) ws_tile[wt_last[q]] = 1;
+    for (uint32_t tl = 0; tl < ntiles; tl++) {
+        if (!tile_alloc[tl]) continue;
+        uint32_t mode = ws_tile[tl] ? gossip::RM_WS : d_nz[nxt] ? gossip::RM_NZ : 0u;
+        if (tl < tr_foldw.size() && tr_foldw[tl]) mode |= tr_seenf[tl] ? gossip::RM_FOLDF : gossip::RM_FOLDS;
+        T[nt++] = tl | (mode << 24);
+        modes |= mode;
+    }
+    for (uint32_t q = 0; q < nwt; q++) T[nt + q] = wt_last[q];
+    if (nt + nwt) HIP_TRY(hipMemcpyAsync(d_rtile[ls], T, (size_t)(nt + nwt) * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_rcnt[ls], 0, (size_t)hw * 256, stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr, es = nullptr;  // pass start, end; k_reach_slots' start
+    if (cfg.flags & GOSSIP_F_TIMING) {
+        e0 = get_event();
+        e1 = get_event();
+        es = get_event();
+        HIP_TRY(hipEventRecord(e0, stream));
+    }
+    const uint64_t rows = v1 - v0;
+    if (nt && rows) {
+        gossip::ReachArgs a;
+        a.F = d_F[nxt]; a.Fprev = d_F[fcur]; a.seen = d_seen;
+        a.nz = d_nz[nxt]; a.slot = young ? d_slot[nxt] : nullptr;
+        a.tiles = d_rtile[ls];
+        a.stride = stride; a.ntw = ntw; a.v0 = v0; a.v1 = v1;
+        // rows per block: 2,048 (128 per lane, one flush) while that gives at most ~4,096 blocks in
+        // all, more beyond -- a block's counts stay in LDS over all its rows, and every block ends
+        // with up to 1,024 global atomics on its tile's columns: at C4, 2,048-row blocks made 360 M
+        // of them per tick on 74 k addresses
+        const uint64_t want_y = std::max<uint64_t>(1, 4096u / nt);
+        uint64_t rpb = std::max<uint64_t>(2048, (rows + want_y - 1) / want_y);
+        rpb = std::min<uint64_t>((rpb + 2047) / 2048 * 2048, 0xfffff800ull);
+        a.rows_per_block = (uint32_t)rpb;
+        a.flush = (uint32_t)opt_reach_flush;
+        a.cnt = d_rcnt[ls]; a.bytes = d_rbytes;
+        gossip::k_reach<<<dim3(nt, (uint32_t)((rows + rpb - 1) / rpb)), 256, 0, stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        ledger.add(gossip::LK_REACH, 16u | modes, false);  // (variant: the tile modes the launch covered)
+    }
+    if (es) HIP_TRY(hipEventRecord(es, stream));
+    if (nwt && rows) {
+        gossip::ReachSlotArgs s;
+        s.slot = d_slot[nxt]; s.wt = d_rtile[ls] + nt; s.nwt = nwt; s.v0 = v0; s.v1 = v1;
+        s.cnt = d_rcnt[ls]; s.bytes = d_rbytes;
+        const uint32_t g = (uint32_t)std::min<uint64_t>((rows + 3) / 4, 16ull * (uint64_t)num_cus);
+        const bool strided = gossip::launch_strides((uint64_t)g * 4u, rows);
+        // counters in LDS for the last kReachSlotLdsTiles write-sparse tiles (plan_young lists them
+        // youngest first: the oldest hold nearly all entries); where the whole set does not fit that
+        // budget, the entries of the younger tiles are one global atomic each
+        s.lds_lo = nwt > gossip::kReachSlotLdsTiles ? nwt - gossip::kReachSlotLdsTiles : 0u;
+        gossip::k_reach_slots<<<g, 256, (size_t)(nwt - s.lds_lo) * 4096, stream>>>(s);
+        HIP_TRY(hipGetLastError());
+        ledger.add(gossip::LK_REACH, s.lds_lo ? 2u : 1u, strided);
+    }
+    if (e0) {
+        HIP_TRY(hipEventRecord(e1, stream));
+        timers_reach.emplace_back(e0, e1);
+        timers_reach_slots.emplace_back(es, e1);  // (e1 is returned to the pool once, by timers_reach)
+    }
+    HIP_TRY(hipMemcpyAsync(h_rcnt[ls], d_rcnt[ls], (size_t)hw * 256, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(reach_done[ls], stream));
+    reach_pending[ls] = true;
+    reach_tick[ls] = t;
+    reach_hw[ls] = hw;
+    return GOSSIP_OK;
+}
+
+// One pending tick's column counts into the (event, hop) bins: a column's source is col_src, its
+// hop the tick less the source's birth tick.  A count in a column without a source is an error.
+int gossip_engine::reach_fold_slot(int ls) {
+    HIP_TRY(hipEventSynchronize(reach_done[ls]));
+    reach_pending[ls] = false;
+    const int64_t t = reach_tick[ls];
+    const uint32_t* C = h_rcnt[ls];
+    const size_t ncol = (size_t)reach_hw[ls] * 64;
+    for (size_t c = 0; c < ncol; c += 2) {
+        uint64_t two;
+        std::memcpy(&two, C + c, 8);
+        if (!two) continue;
+        for (size_t k = c; k < c + 2; k++) {
+            if (!C[k]) continue;
+            const uint32_t src = k < col_src.size() ? col_src[k] : UINT32_MAX;
+            if (src == UINT32_MAX)
+                return set_error(GOSSIP_ESTATE, "reach: tick " + std::to_string(t) + " counted " + std::to_string(C[k]) +
+                                                    " first contacts in column " + std::to_string(k) + ", which has no source event");
+            const int64_t hop = t - ev[src].ns / L;
+            if (hop < 0)
+                return set_error(GOSSIP_ESTATE, "reach: tick " + std::to_string(t) + " counted first contacts in column " +
+                                                    std::to_string(k) + " before its source's birth tick");
+            reach_add(src, hop, C[k]);
+        }
+    }
+    return GOSSIP_OK;
+}
+
+int gossip_engine::reach_fold_upto(int64_t kt) {
+    for (;;) {
+        int best = -1;
+        for (int k = 0; k < kRing; k++)
+            if (reach_pending[k] && reach_tick[k] <= kt && (best < 0 || reach_tick[k] < reach_tick[best])) best = k;
+        if (best < 0) return GOSSIP_OK;
+        if (int rc = reach_fold_slot(best)) return rc;
+    }
+}
+
+int gossip_engine::reach_drain() {
+    HIP_TRY(hipStreamSynchronize(stream));
+    return reach_fold_upto(INT64_MAX);
 }
 
 int gossip_engine::decode_trace(int64_t t) {
@@ -3631,6 +3854,13 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
         e->opt_peer_order = env_option("GOSSIP_PEER_ORDER", 1) != 0 ? 1 : 0;
         e->opt_pull_batch = env_option("GOSSIP_PULL_BATCH", 0) != 0 ? 1 : 0;
         e->opt_seen_fold = std::max<int64_t>(-1, std::min<int64_t>(1, env_option("GOSSIP_SEEN_FOLD", -1)));
+        e->opt_reach_hops = std::max<int64_t>(2, std::min<int64_t>(1024, env_option("GOSSIP_REACH_HOPS", 32)));
+        e->opt_reach_shares = env_option("GOSSIP_REACH_SHARES", 1) != 0 ? 1 : 0;
+        e->opt_reach_flush = std::max<int64_t>(1, std::min<int64_t>(gossip::kReachCap, env_option("GOSSIP_REACH_FLUSH", gossip::kReachCap)));
+        // (GOSSIP_REACH=1 in the environment sets the flag for engines created without it: profiling
+        //  an unchanged driver, tools/bench_reach.py)
+        if (env_option("GOSSIP_REACH", 0) != 0) e->cfg.flags |= GOSSIP_F_REACH;
+        e->reach = (e->cfg.flags & GOSSIP_F_REACH) != 0;
         e->trace = (cfg->flags & GOSSIP_F_TRACE) != 0;
         e->dense = cfg->mode == GOSSIP_MODE_DENSE;
         e->handshake = (cfg->flags & GOSSIP_F_HANDSHAKE) != 0;
@@ -4084,6 +4314,17 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
     } else if (k == "dense_min_tiles") {
         if (value < 1) return set_error(GOSSIP_EINVAL, "dense_min_tiles >= 1");
         e->opt_dense_min_tiles = value;
+    } else if (k == "reach_hops") {
+        if (value < 2 || value > 1024) return set_error(GOSSIP_EINVAL, "reach_hops: 2 .. 1024 bins");
+        if (e->have_sched) return set_error(GOSSIP_ESTATE, "reach_hops: set before the schedule");
+        e->opt_reach_hops = value;
+    } else if (k == "reach_shares") {
+        if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "reach_shares: 0 or 1");
+        if (e->have_sched) return set_error(GOSSIP_ESTATE, "reach_shares: set before the schedule");
+        e->opt_reach_shares = value;
+    } else if (k == "reach_flush") {
+        if (value < 1 || value > (int64_t)gossip::kReachCap) return set_error(GOSSIP_EINVAL, "reach_flush: 1 .. 255 rows");
+        e->opt_reach_flush = value;
     } else {
         return set_error(GOSSIP_EINVAL, "unknown option '" + k + "'");
     }
@@ -4104,7 +4345,8 @@ int gossip_engine_get_option(const gossip_engine* e, const char* name, int64_t* 
         {"xchunks", e->opt_xchunks}, {"rehearse_rows", e->opt_rehearse_rows},
         {"dense_fused", e->opt_dense_fused}, {"dense_min_tiles", e->opt_dense_min_tiles},
         {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch},
-        {"seen_fold", e->opt_seen_fold}};
+        {"seen_fold", e->opt_seen_fold}, {"reach_hops", e->opt_reach_hops},
+        {"reach_shares", e->opt_reach_shares}, {"reach_flush", e->opt_reach_flush}};
     for (const auto& o : opts)
         if (k == o.first) {
             *value = o.second;
@@ -4354,6 +4596,27 @@ int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const goss
         }
         rc = e->alloc_device();
         if (rc) return rc;
+        if (e->reach) {
+            // The engine filtered, re-timed (hop batches), re-sorted and compacted the events: the
+            // caller's index of each, by its (real time, node) key -- unique, checked above.
+            const size_t m = e->ev.size();
+            auto key_ns = [&](uint32_t k) { return e->batch ? e->ev_orig_ns[k] : e->ev[k].ns; };
+            std::vector<uint32_t> by_key(m);
+            std::iota(by_key.begin(), by_key.end(), 0u);
+            std::sort(by_key.begin(), by_key.end(), [&](uint32_t a, uint32_t b) {
+                return key_ns(a) != key_ns(b) ? key_ns(a) < key_ns(b) : e->ev[a].node < e->ev[b].node;
+            });
+            e->reach_of.assign(num_events, UINT32_MAX);
+            for (uint64_t i = 0; i < num_events; i++) {
+                const gossip_gen_event& x = ev[i];
+                auto it = std::lower_bound(by_key.begin(), by_key.end(), x, [&](uint32_t a, const gossip_gen_event& y) {
+                    return key_ns(a) != y.ns ? key_ns(a) < y.ns : e->ev[a].node < y.node;
+                });
+                if (it != by_key.end() && key_ns(*it) == x.ns && e->ev[*it].node == x.node) e->reach_of[i] = *it;
+            }
+            e->reach_tot.assign((size_t)e->opt_reach_hops, 0ull);
+            if (e->opt_reach_shares) e->reach_tab.assign(m * (size_t)e->opt_reach_hops, 0u);
+        }
         if (e->batch) e->tick_end = INT64_MAX / 4;  // runs until every flood has retired
     } catch (const std::bad_alloc&) {
         return set_error(GOSSIP_ENOMEM, "host allocation failed");
@@ -4406,6 +4669,7 @@ int gossip_engine_sync(gossip_engine* e) {
     if (!e) return set_error(GOSSIP_EINVAL, "NULL engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->reach) return e->reach_drain();
     return GOSSIP_OK;
 }
 
@@ -4599,6 +4863,33 @@ int gossip_engine_get_counters(gossip_engine* e, gossip_counters* c) {
     c->pull_sat = e->sat_used ? 1u : 0u;
     c->window_early_retires = e->early_retires;
     c->pull_fold_rows = acct[33];
+    if (e->reach) {
+        double sms = e->reach_slots_ms_done;
+        for (auto& p : e->timers_reach_slots) {  // (before timers_reach gives the shared end events back)
+            float x = 0.f;
+            HIP_TRY(hipEventElapsedTime(&x, p.first, p.second));
+            sms += x;
+            e->event_pool.push_back(p.first);
+        }
+        e->timers_reach_slots.clear();
+        e->reach_slots_ms_done = sms;
+        c->reach_slots_ms = sms;
+        double rms = e->reach_ms_done;
+        for (auto& p : e->timers_reach) {
+            float x = 0.f;
+            HIP_TRY(hipEventElapsedTime(&x, p.first, p.second));
+            rms += x;
+            e->event_pool.push_back(p.first);
+            e->event_pool.push_back(p.second);
+        }
+        e->timers_reach.clear();
+        e->reach_ms_done = rms;
+        c->reach_ms = rms;
+        c->reach_launches = e->reach_launches;
+        unsigned long long rb = 0ull;
+        if (e->d_rbytes) HIP_TRY(hipMemcpy(&rb, e->d_rbytes, 8, hipMemcpyDeviceToHost));
+        c->reach_bytes = rb;
+    }
     uint64_t g = 0;
     const uint64_t done = (uint64_t)std::max<int64_t>(0, std::min(e->cur, e->tick_end) - e->tick0);
     if (!e->tick_lo.empty()) g = e->tick_lo[std::min<uint64_t>(done, e->tick_lo.size() - 1)];
@@ -4663,6 +4954,16 @@ int gossip_engine_reset_timing(gossip_engine* e) {
     }
     e->timers_phase.clear();
     e->phase_ms_done = 0.0;
+    for (auto& p : e->timers_reach) {
+        e->event_pool.push_back(p.first);
+        e->event_pool.push_back(p.second);
+    }
+    e->timers_reach.clear();
+    e->reach_ms_done = 0.0;
+    for (auto& p : e->timers_reach_slots) e->event_pool.push_back(p.first);
+    e->timers_reach_slots.clear();
+    e->reach_slots_ms_done = 0.0;
+    if (e->d_rbytes) HIP_TRY(hipMemsetAsync(e->d_rbytes, 0, 8, e->stream));
     if (e->d_phase_ts) HIP_TRY(hipMemsetAsync(e->d_phase_ts + 2, 0, 16, e->stream));
     e->rehearse_harvest();  // (row-partition rehearsal: restart the per-range sums)
     for (auto& v : e->rr_ms) std::fill(v.begin(), v.end(), 0.0);
@@ -4726,6 +5027,43 @@ int gossip_engine_get_trace(const gossip_engine* e, uint32_t* node, uint32_t* sh
         if (tick) tick[k] = r.tick;
         if (hop) hop[k] = r.hop;
         if (via_recv) via_recv[k] = r.via;
+    }
+    return GOSSIP_OK;
+}
+
+static int check_reach(gossip_engine* e) {
+    if (!e) return set_error(GOSSIP_EINVAL, "NULL engine");
+    if (!e->reach) return set_error(GOSSIP_ESTATE, "reach profiles need GOSSIP_F_REACH");
+    if (!e->have_sched) return set_error(GOSSIP_ESTATE, "no schedule");
+    HIP_TRY(hipSetDevice(e->device));
+    return e->reach_drain();
+}
+
+int gossip_engine_get_reach_totals(gossip_engine* e, uint32_t cap_hops, uint64_t* by_hop, uint32_t* hops) {
+    if (int rc = check_reach(e)) return rc;
+    const uint32_t H = (uint32_t)e->opt_reach_hops;
+    if (hops) *hops = H;
+    if (!by_hop) return GOSSIP_OK;
+    if (cap_hops < H) return set_error(GOSSIP_EINVAL, "get_reach_totals: " + std::to_string(H) + " bins, room for " + std::to_string(cap_hops));
+    std::memcpy(by_hop, e->reach_tot.data(), (size_t)H * 8);
+    return GOSSIP_OK;
+}
+
+int gossip_engine_get_reach(gossip_engine* e, uint64_t first_event, uint64_t num_events, uint32_t* out) {
+    if (int rc = check_reach(e)) return rc;
+    if (!e->opt_reach_shares) return set_error(GOSSIP_ESTATE, "get_reach: the per-event table is off (option reach_shares 0)");
+    const uint64_t m = e->reach_of.size();
+    if (first_event > m || num_events > m - first_event)
+        return set_error(GOSSIP_EINVAL, "get_reach: events [" + std::to_string(first_event) + ", +" + std::to_string(num_events) +
+                                            ") of a schedule of " + std::to_string(m));
+    if (num_events && !out) return set_error(GOSSIP_EINVAL, "NULL argument");
+    const size_t H = (size_t)e->opt_reach_hops;
+    for (uint64_t i = 0; i < num_events; i++) {
+        const uint32_t k = e->reach_of[first_event + i];
+        if (k == UINT32_MAX)
+            std::memset(out + i * H, 0, H * 4);
+        else
+            std::memcpy(out + i * H, e->reach_tab.data() + (size_t)k * H, H * 4);
     }
     return GOSSIP_OK;
 }

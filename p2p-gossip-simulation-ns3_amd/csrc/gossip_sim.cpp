@@ -56,6 +56,7 @@ struct Options {
     std::string layout = "shards";     // shards | rows
     double memLimitMB = 0;             // device memory budget per engine (0: the device's)
     std::string schedule = "exact";    // exact (the reference's mt19937 stream) | philox (GPU)
+    std::string reach;                 // reach profile per counted event (GOSSIP_F_REACH)
 };
 
 void usage() {
@@ -68,7 +69,7 @@ void usage() {
                  "                  [--mode=auto|csr|dense] [--dumpLinks=F] [--dumpEvents=F]\n"
                  "                  [--links=F] [--events=F] [--dumpTrace=F] [--netanim=F] [--noPackets]\n"
                  "                  [--log=F|-] [--gpus=N] [--shards=S] [--layout=shards|rows]\n"
-                 "                  [--memLimitMB=M] [--schedule=exact|philox]\n");
+                 "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n");
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -137,6 +138,7 @@ bool parse(int argc, char** argv, Options& o) {
         else if (key == "layout") { if (!need()) return false; o.layout = val; }
         else if (key == "memLimitMB") { if (!num(o.memLimitMB) || o.memLimitMB < 0) return false; }
         else if (key == "schedule") { if (!need()) return false; o.schedule = val; }
+        else if (key == "reach") { if (!need()) return false; o.reach = val; }
         else {
             std::fprintf(stderr, "unknown option --%s\n", key.c_str());
             return false;
@@ -159,6 +161,8 @@ struct Part {
     std::vector<uint32_t> tn, ti, th;
     std::vector<int64_t> tt;
     std::vector<uint8_t> tv;
+    std::vector<uint32_t> reach;  // --reach: events x reach_hops (this engine's rows / shares)
+    uint32_t reach_hops = 0;
     gossip_counters c{};
     int64_t first_tick = 0, end_tick = 0;
     int rc = 0;
@@ -267,6 +271,12 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
     if (m && (rc = gossip_engine_get_trace(eng, out.tn.data(), out.ti.data(), out.tt.data(), out.th.data(),
                                            out.tv.data())))
         return fail("trace", rc);
+    if (cfg.flags & GOSSIP_F_REACH) {
+        if ((rc = gossip_engine_get_reach_totals(eng, 0, nullptr, &out.reach_hops))) return fail("reach", rc);
+        const uint64_t me = gossip_schedule_size(sched);
+        out.reach.assign((size_t)me * out.reach_hops, 0u);
+        if (me && (rc = gossip_engine_get_reach(eng, 0, me, out.reach.data()))) return fail("reach", rc);
+    }
     gossip_engine_get_counters(eng, &out.c);
     gossip_engine_destroy(eng);
 }
@@ -349,7 +359,8 @@ int main(int argc, char** argv) {
     const bool anim_packets = !o.netanim.empty() && n <= 128849u && !o.noPackets;
     const bool want_trace = !(o.dumpTrace.empty() && o.log.empty()) || anim_packets;
     cfg.flags = (o.timing ? GOSSIP_F_TIMING : 0u) | (o.handshake ? GOSSIP_F_HANDSHAKE : 0u) |
-                (o.hopBatch ? GOSSIP_F_HOP_BATCH : 0u) | (want_trace ? GOSSIP_F_TRACE : 0u);
+                (o.hopBatch ? GOSSIP_F_HOP_BATCH : 0u) | (want_trace ? GOSSIP_F_TRACE : 0u) |
+                (o.reach.empty() ? 0u : GOSSIP_F_REACH);
     if (!o.log.empty() && o.handshake) {
         std::fprintf(stderr, "gossip_sim: --log renders the ideal / --linkTiming models, not --handshake\n");
         return 2;
@@ -499,6 +510,41 @@ int main(int argc, char** argv) {
         if (!f) { std::perror(o.dumpTrace.c_str()); return 1; }
         for (uint64_t k = 0; k < m; k++)
             std::fprintf(f, "%u %u %lld %u %u\n", tn[k], ti[k], (long long)tt[k], th[k], (unsigned)tv[k]);
+        std::fclose(f);
+    }
+    if (!o.reach.empty()) {
+        // One line per counted event, in schedule order: "ns node shareId reached h50 h90 hlast"
+        // then the counts per hop c0 c1 ... up to the last non-zero bin -- reached = nodes that took
+        // the share from this generation (itself included), hNN = the first hop at which the
+        // cumulative count reaches NN % of reached, hlast = the last hop with a first contact (-1
+        // each for an event that reached nobody).  Summed over share shards and row ranks.
+        std::vector<gossip_gen_event> ev(gossip_schedule_size(sched));
+        if (!ev.empty()) gossip_schedule_get(sched, ev.data());
+        const uint32_t H = parts[0].reach_hops;
+        FILE* f = std::fopen(o.reach.c_str(), "w");
+        if (!f) { std::perror(o.reach.c_str()); return 1; }
+        std::vector<uint64_t> row(H);
+        for (size_t k = 0; k < ev.size(); k++) {
+            uint64_t total = 0;
+            int last = -1;
+            for (uint32_t h = 0; h < H; h++) {
+                row[h] = 0;
+                for (const Part& p : parts) row[h] += p.reach[k * H + h];
+                total += row[h];
+                if (row[h]) last = (int)h;
+            }
+            int h50 = -1, h90 = -1;
+            uint64_t cum = 0;
+            for (uint32_t h = 0; h < H && total; h++) {
+                cum += row[h];
+                if (h50 < 0 && 2 * cum >= total) h50 = (int)h;
+                if (h90 < 0 && 10 * cum >= 9 * total) h90 = (int)h;
+            }
+            std::fprintf(f, "%lld %u %u %llu %d %d %d", (long long)ev[k].ns, ev[k].node, ev[k].share_id,
+                         (unsigned long long)total, h50, h90, last);
+            for (int h = 0; h <= last; h++) std::fprintf(f, " %llu", (unsigned long long)row[h]);
+            std::fputc('\n', f);
+        }
         std::fclose(f);
     }
     gossip_counters c{};

@@ -15,8 +15,8 @@
 namespace gossip {
 
 // kernels the ledger records (gossip.h: GOSSIP_K_*)
-enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4 };
-constexpr uint32_t kLaunchKernels = 5;
+enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4, LK_REACH = 5 };
+constexpr uint32_t kLaunchKernels = 6;
 
 // k_pull's template flags (gossip.h: GOSSIP_PULL_*)
 enum : uint32_t { PK_NT = 1u, PK_SP = 2u, PK_PUSH = 4u, PK_SHORT = 8u, PK_FOLD = 16u };

@@ -37,6 +37,7 @@ F_TILE_PER_TICK = 32
 F_HANDSHAKE = 64
 F_HOP_BATCH = 128
 F_SHARD_BY_TICK = 256
+F_REACH = 512
 
 EXPORTED_SYMBOLS = (
     "gossip_last_error", "gossip_version", "gossip_seconds_to_ns", "gossip_milliseconds_to_ns",
@@ -61,10 +62,11 @@ EXPORTED_SYMBOLS = (
     "gossip_format_netanim", "gossip_topology_load_links", "gossip_schedule_load_events",
     "gossip_engine_abort", "gossip_engine_get_rehearsal", "gossip_engine_get_rehearsal_peak",
     "gossip_engine_get_option", "gossip_engine_get_launches", "gossip_pull_instantiations",
+    "gossip_engine_get_reach_totals", "gossip_engine_get_reach",
 )
 
 # launch ledger (gossip.h): kernel ids and k_pull's template flags
-K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP = range(5)
+K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP, K_REACH = range(6)
 PULL_NT, PULL_SP, PULL_PUSH, PULL_SHORT, PULL_FOLD = 1, 2, 4, 8, 16
 
 # NS-3 5 Mbps point-to-point links (p2pnetwork.cc:113): ns per byte, PPP+IPv4+TCP(timestamp
@@ -122,6 +124,8 @@ class gossip_counters(C.Structure):
         ("young_grid", C.c_uint32), ("young_skip_ticks", C.c_uint32),
         ("pull_push_tiles", C.c_uint64), ("pull_pushw_tiles", C.c_uint64), ("pull_marks", C.c_uint64),
         ("young_idle_ticks", C.c_uint64), ("pull_fold_rows", C.c_uint64),
+        ("reach_launches", C.c_uint64), ("reach_ms", C.c_double), ("reach_bytes", C.c_uint64),
+        ("reach_slots_ms", C.c_double),
     ]
 
 
@@ -244,6 +248,8 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_reset_timing": (C.c_int, [P]),
         "gossip_engine_trace_size": (u64, [P]),
         "gossip_engine_get_trace": (C.c_int, [P, P, P, P, P, P]),
+        "gossip_engine_get_reach_totals": (C.c_int, [P, u32, P, C.POINTER(u32)]),
+        "gossip_engine_get_reach": (C.c_int, [P, u64, u64, P]),
         "gossip_engine_destroy": (None, [P]),
         "gossip_format_statistics": (i64, [u32, P, P, P, P, P, P, P, C.c_char_p, u64]),
         "gossip_format_periodic": (i64, [C.c_double, u32, u64, u64, u64, C.c_char_p, u64]),
@@ -548,6 +554,7 @@ class Engine:
     def set_schedule(self, ev: np.ndarray):
         ev = np.ascontiguousarray(ev, GEN_EVENT_DTYPE)
         _check(load_library().gossip_engine_set_schedule(self._h, ev.size, _vp(ev)), "set schedule")
+        self.num_events = int(ev.size)
 
     @property
     def mode(self) -> int:
@@ -632,6 +639,28 @@ class Engine:
                                                _vp(via)), "trace")
         return node, sid, tick, hop, via
 
+    def reach_totals(self) -> np.ndarray:
+        """Reach profile summed over events (F_REACH): first contacts by hop, uint64 (hops,)."""
+        lib = load_library()
+        h = C.c_uint32()
+        _check(lib.gossip_engine_get_reach_totals(self._h, 0, None, C.byref(h)), "reach totals")
+        out = np.zeros(h.value, np.uint64)
+        _check(lib.gossip_engine_get_reach_totals(self._h, h.value, _vp(out), C.byref(h)), "reach totals")
+        return out
+
+    def reach(self, first_event: int = 0, num_events: int | None = None) -> np.ndarray:
+        """Reach profile (F_REACH): (events, hops) uint32, row k = the events[k] given to
+        set_schedule, column h = nodes first reached from its column at hop h (the last bin: every
+        later hop).  Sum over row-partition ranks and over share shards."""
+        lib = load_library()
+        h = C.c_uint32()
+        _check(lib.gossip_engine_get_reach_totals(self._h, 0, None, C.byref(h)), "reach")
+        if num_events is None:
+            num_events = getattr(self, "num_events", 0) - int(first_event)
+        out = np.zeros((max(int(num_events), 0), h.value), np.uint32)
+        _check(lib.gossip_engine_get_reach(self._h, int(first_event), int(num_events), _vp(out)), "reach")
+        return out
+
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.gossip_engine_destroy(self._h)
@@ -639,6 +668,22 @@ class Engine:
 
     def __del__(self):
         self.close()
+
+
+def coverage_hops(reach, frac: float) -> np.ndarray:
+    """Per row of a reach profile (events x hops), the first hop at which the cumulative count
+    reaches `frac` of the row's final reach (its sum); -1 for an all-zero row.  Pure numpy.  A
+    cumulative count equal to frac x sum counts as reached: frac is taken as the nearest fraction
+    with a denominator up to 10^5 (0.9 = 9/10) and compared in integers."""
+    from fractions import Fraction
+    f = Fraction(float(frac)).limit_denominator(100000)
+    r = np.atleast_2d(np.asarray(reach)).astype(np.uint64)
+    total = r.sum(axis=1)
+    cum = np.cumsum(r, axis=1)
+    hit = cum * np.uint64(f.denominator) >= (total * np.uint64(max(f.numerator, 0)))[:, None]
+    out = np.where(hit.any(axis=1), hit.argmax(axis=1), -1).astype(np.int64)
+    out[total == 0] = -1
+    return out
 
 
 def format_event_log(topo: "Topology", ev: np.ndarray, trace, latency_ns: int, t_start_ns: int,
@@ -745,9 +790,9 @@ class P2PGossipNetworkSimulation:
                                      self.threads)
         self.latency_ns = milliseconds_to_ns(latency)
 
-    def _run_shard(self, ev, t_start, t_cut, snaps, rank, count):
+    def _run_shard(self, ev, t_start, t_cut, snaps, rank, count, reach=False):
         eng = Engine(self.numNodes, self.latency_ns, t_start, t_cut, device=self.device,
-                     flags=self.flags, shard_rank=rank, shard_count=count)
+                     flags=self.flags | (F_REACH if reach else 0), shard_rank=rank, shard_count=count)
         for k, v in self.options.items():
             eng.set_option(k, v)
         eng.set_topology(self.topology)
@@ -760,12 +805,13 @@ class P2PGossipNetworkSimulation:
         eng.sync()
         return eng
 
-    def Start(self, simulationTime: float = 100.0, statsInterval: float = 10.0, events=None):
+    def Start(self, simulationTime: float = 100.0, statsInterval: float = 10.0, events=None, reach=False):
         """Run the simulation (p2pnetwork.cc:193-218).  The share instances run as `shards`
         engines one after another (counters add exactly); when an engine's live window does not
         fit the device (GOSSIP_ECAPACITY / GOSSIP_ENOMEM) the shard count doubles and the run
         restarts.  `events` (GEN_EVENT_DTYPE) replays a given schedule instead of the reference's
-        (e.g. one dumped from an NS-3 run)."""
+        (e.g. one dumped from an NS-3 run).  reach=True (F_REACH) keeps the reach profile summed
+        over the shards as self.reach (events x hops, rows in the order of self.events)."""
         if self.topology is None:
             raise GossipError("CreateRandomTopology first")
         t_start = seconds_to_ns(5.0)
@@ -781,9 +827,12 @@ class P2PGossipNetworkSimulation:
         while True:
             try:
                 parts = []
+                prof = None
                 for r in range(count):
-                    eng = self._run_shard(ev, t_start, t_cut, times, r, count)
+                    eng = self._run_shard(ev, t_start, t_cut, times, r, count, reach)
                     parts.append((eng.stats(), [eng.snapshot(k) for k in range(len(times))]))
+                    if reach:
+                        prof = eng.reach() if prof is None else prof + eng.reach()
                     if r + 1 < count:
                         eng.close()  # keep only the last engine (counters, trace) alive
                 break
@@ -793,6 +842,8 @@ class P2PGossipNetworkSimulation:
                 count *= 2
         self.shards_used = count
         self.engine = eng
+        self.events = ev
+        self.reach = prof
         st = parts[0][0]
         if count > 1:  # counters add exactly over share shards
             st = Stats(*(sum(getattr(p[0], k).astype(np.uint64) for p in parts).astype(getattr(st, k).dtype)
