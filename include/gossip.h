@@ -282,6 +282,54 @@ int gossip_engine_tick_end(gossip_engine* e);
 int gossip_engine_set_link_timing(gossip_engine* e, int64_t ns_per_byte, uint32_t header_bytes,
                                   int64_t send_defer_ns);
 uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t t_ns);
+
+/* Fanout-limited gossip: the flood model with one change -- a Send from node u to peer v, copy c
+ * (c < the multiplicity of v in u's list: a parallel link is two independent copies), made in tick
+ * T = floor(send time / latency), happens only if it is selected:
+ *     lo = min(u, v), hi = max(u, v)
+ *     x  = Philox4x32-10(counter = (lo, hi, (uint32)T, c),
+ *                        key = (seed & 0xffffffff, (seed >> 32) ^ 0x46414E4F))
+ *     w  = (u < v) ? x[0] : x[1]
+ *     selected = (thr[u] == 0xffffffff) || (w < thr[u])
+ * thr[u] is the sender's threshold: it forwards with probability thr / 2^32 (0xffffffff always, 0
+ * never).  The draw belongs to (sender, receiver, copy, tick), NOT to a share: everything a node
+ * sends in one tick shares one draw per (peer, copy) -- the round-based push model, "each round a
+ * node pushes its new items to a few peers".  A share generated at g is sent in tick floor(g / L); a
+ * first arrival at hop h forwards in tick floor(g / L) + h.  Unselected Sends are not made: they are
+ * not counted in sent or edge_events and deliver nothing; recv, fwd, processed, the trace, snapshots,
+ * reach profiles and the cut keep their meaning.  The result is a pure function of (graph, events,
+ * latency, cut, thr, seed): no tuning option, tile layout or share sharding changes it (share shards
+ * add up to the single engine).
+ *   gossip_engine_set_fanout(k): thr[u] = 0xffffffff if deg(u) <= k, else floor(k * 2^32 / deg(u)),
+ * deg = the sum of multiplicities of u's row: an EXPECTED fanout of k, binomial.  An exact k-subset
+ * is not offered: it needs v's position in u's list and u's degree per entry, two more random
+ * gathers per entry and tick.
+ *   gossip_engine_set_forward_thresholds: thr[n] given by the caller.
+ * Both: after the graph and before the schedule (GOSSIP_ESTATE otherwise); every buffer of the mode
+ * is allocated here.  Share ids must be unique (gossip_engine_set_schedule returns GOSSIP_EINVAL
+ * naming the first collision; ids are only seen-set keys, so callers renumber them).  Refused with
+ * GOSSIP_EINVAL: GOSSIP_F_HOP_BATCH (hence link timing), GOSSIP_F_HANDSHAKE, a row partition,
+ * GOSSIP_MODE_DENSE (AUTO resolves to CSR), ticks beyond 32 bits, and forcing on the options young,
+ * pull_push, young_skip or young_idle (their auto values resolve to off; seen_fold resolves to off
+ * too, with results unchanged).  Every tick ends with two kernel passes and a scan over the peer
+ * lists (k_fanout, csrc/fanout_kernel.h), with no host round trip; the next tick's pull reads the
+ * thinned lists.
+ *   gossip_fanout_selected: the rule itself, 1 / 0; needs no engine and no device. */
+int gossip_engine_set_fanout(gossip_engine* e, uint32_t fanout /* >= 1 */, uint64_t seed);
+int gossip_engine_set_forward_thresholds(gossip_engine* e, const uint32_t* thr /* n */, uint64_t seed);
+int gossip_fanout_selected(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy,
+                           int64_t tick, uint32_t thr);
+typedef struct gossip_fanout_counters {
+    uint64_t launches;      /* ticks whose Sends were selected (count pass + scan + compact pass) */
+    uint64_t selected_in;   /* peer-list entries kept, summed over ticks                          */
+    uint64_t selected_out;  /* selected out-copies, summed over nodes and ticks                   */
+    uint64_t entries;       /* peer-list entries examined, summed over ticks                      */
+    double ms;              /* summed HIP-event time of those launches (GOSSIP_F_TIMING)          */
+    uint64_t bytes;         /* bytes they had to move (model: 9 B + 2 bits per entry, 68 B per
+                               node, 8 B per kept entry)                                          */
+} gossip_fanout_counters;
+/* Since the last gossip_engine_reset_timing; zeros on an engine without fanout. */
+int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* c);
 /* Tuning options of one engine (results never depend on them; A/B runs and tests).  The
  * environment variable in brackets gives the default:
  *   "pull_nt"          -1 auto (non-temporal rows when the live frontier n x wact x 8 B exceeds
@@ -366,6 +414,9 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  *   "reach_flush"      reach profiles, tests: rows a lane of k_reach adds to its bit planes between
  *                      flushes, 1..255 (255, the planes' capacity): small values make small graphs
  *                      cross flush boundaries                              [GOSSIP_REACH_FLUSH]
+ *   "fanout_grid"      fanout mode: blocks of the two k_fanout passes, 0 = auto (one wave per 64 nodes,
+ *                      at most 64 blocks per compute unit); small values make a wave loop over
+ *                      several 64-node chunks (tests)                      [GOSSIP_FANOUT_GRID]
  *   "xchunks"          row partition: row chunks per tick of the pipelined exchange, 1..16 (4);
  *                      equal on every rank of a partition                    [GOSSIP_XCHUNKS]
  *   "rehearse_rows"    diagnostic, R >= 2 on an unpartitioned CSR engine (before the schedule;
@@ -503,7 +554,9 @@ int gossip_engine_reset_timing(gossip_engine* e);
  *             bits, 2 write-sparse tiles (overflowed nodes' rows), 4 folded rows masked with the
  *             other frontier buffer, 8 folded rows masked with seen rows; 1 k_reach_slots with every
  *             counter in LDS, 2 k_reach_slots with more than 8 write-sparse tiles (the 8 oldest
- *             tiles' counters in LDS, a global atomic per entry of the others); 0 otherwise
+ *             tiles' counters in LDS, a global atomic per entry of the others); GOSSIP_K_FANOUT: 1 the
+ *             count pass, 2 the compact pass (strided: a wave looped over several 64-node chunks);
+ *             0 otherwise
  *   launches  launches of that variant
  *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's
  *             grid-stride loop ran more than once: k_pull, k_pull_young and k_young_idle 4 x blocks <
@@ -517,6 +570,7 @@ int gossip_engine_reset_timing(gossip_engine* e);
 #define GOSSIP_K_DENSE_BITS 3
 #define GOSSIP_K_DENSE_DEDUP 4
 #define GOSSIP_K_REACH 5      /* k_reach / k_reach_slots (GOSSIP_F_REACH only) */
+#define GOSSIP_K_FANOUT 6     /* k_fanout_count / k_fanout_compact (fanout mode only) */
 #define GOSSIP_PULL_NT 1u     /* non-temporal row accesses                  */
 #define GOSSIP_PULL_SP 2u     /* tile masks, saturation bits (32 x 1 lanes) */
 #define GOSSIP_PULL_PUSH 4u   /* push marks                                 */

@@ -50,6 +50,7 @@
 #include "pull_plan.h"
 #include "launch_ledger.h"
 #include "reach_kernel.h"
+#include "fanout_kernel.h"
 
 using gossip::set_error;
 using gossip::PullShape;
@@ -1018,6 +1019,36 @@ struct gossip_engine {
         reach_tot[h] += c;
         if (opt_reach_shares) reach_tab[(size_t)src * (size_t)H + h] += c;
     }
+    // ---- fanout-limited gossip (gossip_engine_set_fanout / _set_forward_thresholds; fanout_kernel.h):
+    // every tick ends with k_fanout_count, a scan and k_fanout_compact, which thin the peer lists to
+    // the tick's selected Sends; the next tick's k_pull walks (d_rowptr_t, d_col_t).  sent is counted
+    // by the count pass (d_sent_f), not derived from recv.  Everything below is allocated by the
+    // setter and by nothing else.
+    bool fanout = false;
+    uint64_t fanout_seed = 0;
+    std::vector<std::pair<uint64_t, uint8_t>> h_multx;  // set_graph: (row << 32 | col, mult) of the entries with mult != 1, sorted
+    uint32_t* d_fthr = nullptr;        // n sender thresholds
+    uint32_t* d_in_thr = nullptr;      // nnz: threshold of the entry's peer
+    uint8_t* d_emult = nullptr;        // nnz: in-multiplicity | out-multiplicity << 4
+    unsigned long long* d_fbitmap = nullptr;
+    uint32_t* d_fcnt = nullptr;        // n + 1
+    int64_t* d_rowptr_t = nullptr;     // n + 1
+    int32_t* d_col_t = nullptr;        // nnz
+    uint32_t *d_recv_prev = nullptr, *d_gen_prev = nullptr;
+    unsigned long long* d_sent_f = nullptr;
+    unsigned long long* d_fstat = nullptr;
+    void* d_fscan_tmp = nullptr;
+    size_t fscan_tmp_bytes = 0;
+    uint64_t fanout_bytes = 0;         // device bytes of the above (in device_bytes)
+    int64_t opt_fanout_grid = 0;       // blocks of the two passes, 0 = auto
+    bool forced_young_idle = false;    // set_option("young_idle", 1) was called
+    uint64_t fanout_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_fanout;
+    double fanout_ms_done = 0.0;
+    int fanout_launch(int64_t t);      // tick_step_b: the selection of tick t, for the pull of t + 1
+    int fanout_setup(const uint32_t* thr, uint64_t seed);
+    void fanout_free();                // every buffer above (a setter call that failed half-way, the destructor)
+    bool fanout_allocated = false;     // the setter's allocations all succeeded
 
     ~gossip_engine();
     int alloc_device();
@@ -1154,6 +1185,11 @@ gossip_engine::~gossip_engine() {
     }
     for (auto& p : timers_reach_slots) hipEventDestroy(p.first);
     hipFree(d_rbytes);
+    for (auto& p : timers_fanout) {
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    fanout_free();
     if (comm && !aborted.load()) ncclCommDestroy(comm);  // (an aborted communicator is already freed)
     for (int k = 0; k < kRing; k++) {
         hipFree(d_ctl[k]); hipFree(d_births[k]); hipFree(d_gphase[k]); hipFree(d_wflags[k]);
@@ -1457,7 +1493,8 @@ int gossip_engine::alloc_device() {
     stride = (words + kTileWords - 1) / kTileWords * kTileWords;  // rows start on 128-B lines
     // Young tiles: the CSR tick pull on graphs whose frontier rows outgrow the caches (C3/C4).
     {
-        const bool ok = !dense && !batch && !handshake && row_count == 1 && opt_rehearse_rows <= 1 &&
+        // (fanout mode: slots and hint bytes are addressed by position in the full peer list)
+        const bool ok = !dense && !batch && !handshake && row_count == 1 && opt_rehearse_rows <= 1 && !fanout &&
                         !(cfg.flags & GOSSIP_F_NOSKIP) &&
                         n < (1u << 31);  // (peer ids carry a hint in bit 31)
         if (opt_young == 1 && !ok)
@@ -1619,6 +1656,7 @@ int gossip_engine::alloc_device() {
     }
     device_bytes = 2 * bm + bm_seen + (d_sat ? 24ull : 16ull) * n * ntw + (uint64_t)n * 20 + nnz * 4 + ((uint64_t)n + 1) * 8 + 2ull * stride * 8 + slot_bytes +
                    kRing * ((uint64_t)stride * sizeof(WordCtl) + (uint64_t)bcap * sizeof(Birth) + pcap * 4);
+    device_bytes += fanout_bytes;  // (allocated by the fanout setter; 0 without one)
     if (dense) {
         const uint64_t ft = (uint64_t)stride * 8 * n_pad;
         snz_nstw = (n_pad / kStageK + 63u) / 64u;
@@ -2358,7 +2396,8 @@ int gossip_engine::build_tile_masks(TickPlan& p) {
     sat_used = p.sat_used;
     last_dense_tiles = 0;
     // push marks ride on the saturation words (an unmarked node's push tiles read as saturated)
-    p.push_on = p.sat_used && opt_pull_push != 0 && d_mark[0];
+    // (fanout mode: a writer marks its own list for its readers, but only the selected ones read it)
+    p.push_on = p.sat_used && opt_pull_push != 0 && d_mark[0] && !fanout;
     // Folded rows (option seen_fold; pull_kernel.h): a sealed tile that is read dense and written whole
     // this tick carries its seen bits in the F_next row (TM_FOLDW), and a tile folded last tick reads
     // them back from F_cur (TM_SEENF).  Only where every tick is one hop of an unmasked, symmetric
@@ -2366,7 +2405,8 @@ int gossip_engine::build_tile_masks(TickPlan& p) {
     // a keep mask has dropped receptions (a dropped column would come back out of a folded row).
     if (p.keep_any) fold_barred = true;
     const bool fold_ok = opt_seen_fold != 0 && p.sat_used && p.dr_used && !fold_barred && !handshake && !batch &&
-                         !link_timing && opt_rehearse_rows <= 1;
+                         !link_timing && opt_rehearse_rows <= 1 &&
+                         !fanout;  // (a seen bit was not sent to every peer: a folded row would deliver it late)
     if (trace || reach) {
         tr_foldw.assign(hw / kTileWords, 0);
         tr_seenf.assign(hw / kTileWords, 0);
@@ -2710,6 +2750,10 @@ int gossip_engine::launch_tick(TickPlan& p) {
         if (handshake && t == tick0 + 3) {  // shares sent in [t_start+2L, t_start+3L): a -> b only
             a.rowptr = d_rowptr_c;
             a.col = d_col_c;
+        }
+        if (fanout) {  // the Sends selected at the end of tick t - 1 (fanout_launch; all rows empty before the first)
+            a.rowptr = d_rowptr_t;
+            a.col = d_col_t;
         }
         a.Fcur = d_F[fcur]; a.Fnext = d_F[nxt]; a.seen = d_seen; a.ctl = d_ctl[slot];
         a.wflags = d_wflags[slot];
@@ -3534,6 +3578,10 @@ int gossip_engine::tick_step_b(int64_t t) {
         int rc = reach_launch(t);
         if (rc) return rc;
     }
+    if (fanout) {  // the tick's selected Sends: sent counts now, the thinned peer lists for the pull of t + 1
+        int rc = fanout_launch(t);
+        if (rc) return rc;
+    }
     // 6. liveness read-back (consumed kLag ticks later)
     {
         const int ls = (int)(t % kRing);
@@ -3721,6 +3769,122 @@ int gossip_engine::reach_drain() {
     return reach_fold_upto(INT64_MAX);
 }
 
+// ---- fanout-limited gossip (fanout_kernel.h) -----------------------------------------------
+// The scan's input: the per-node in-counts as int64, so that the row pointers are summed in 64 bits
+struct FanoutCountCast {
+    __host__ __device__ int64_t operator()(uint32_t x) const { return (int64_t)x; }
+};
+using FanoutCountIt = hipcub::TransformInputIterator<int64_t, FanoutCountCast, const uint32_t*>;
+
+// Thresholds, per-entry side arrays and every per-tick buffer of fanout mode (the setters; a second
+// call before the schedule re-fills the same buffers)
+void gossip_engine::fanout_free() {
+    hipFree(d_fthr); hipFree(d_in_thr); hipFree(d_emult); hipFree(d_fbitmap); hipFree(d_fcnt); hipFree(d_rowptr_t);
+    hipFree(d_col_t); hipFree(d_recv_prev); hipFree(d_gen_prev); hipFree(d_sent_f); hipFree(d_fstat); hipFree(d_fscan_tmp);
+    d_fthr = d_in_thr = d_fcnt = d_recv_prev = d_gen_prev = nullptr;
+    d_emult = nullptr;
+    d_fbitmap = d_sent_f = d_fstat = nullptr;
+    d_rowptr_t = nullptr;
+    d_col_t = nullptr;
+    d_fscan_tmp = nullptr;
+    fscan_tmp_bytes = 0;
+}
+
+int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed) {
+    HIP_TRY(hipSetDevice(device));
+    std::vector<uint32_t> in_thr(nnz);
+    std::vector<uint8_t> em(nnz);
+    auto mult_of = [&](uint32_t row, uint32_t c) -> uint32_t {
+        const uint64_t key = ((uint64_t)row << 32) | c;
+        auto it = std::lower_bound(h_multx.begin(), h_multx.end(), std::make_pair(key, (uint8_t)0));
+        return it != h_multx.end() && it->first == key ? it->second : 1u;
+    };
+    for (uint32_t v = 0; v < n; v++)
+        for (int64_t j = h_rowptr[v]; j < h_rowptr[v + 1]; j++) {
+            const uint32_t u = (uint32_t)h_col[j];
+            const uint32_t mo = h_multx.empty() ? 1u : mult_of(v, u), mi = h_multx.empty() ? 1u : mult_of(u, v);
+            if (mo > 15u || mi > 15u)
+                return set_error(GOSSIP_EINVAL, "fanout: multiplicity above 15 at row " + std::to_string(v) + ", col " + std::to_string(u));
+            in_thr[j] = thr[u];
+            em[j] = (uint8_t)(mi | (mo << 4));
+        }
+    if (!fanout_allocated) {
+        fanout_free();  // (what an earlier call that failed half-way left)
+        const size_t n1 = (size_t)n + 1, e1 = std::max<size_t>(nnz, 1), bw = (size_t)(nnz + 63) / 64 + 1;
+        const size_t statb = (size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas * 8;
+        HIP_TRY(hipMalloc(&d_fthr, n1 * 4));
+        HIP_TRY(hipMalloc(&d_in_thr, e1 * 4));
+        HIP_TRY(hipMalloc(&d_emult, e1));
+        HIP_TRY(hipMalloc(&d_fbitmap, bw * 8));
+        HIP_TRY(hipMalloc(&d_fcnt, n1 * 4));
+        HIP_TRY(hipMalloc(&d_rowptr_t, n1 * 8));
+        HIP_TRY(hipMalloc(&d_col_t, e1 * 4));
+        HIP_TRY(hipMalloc(&d_recv_prev, n1 * 4));
+        HIP_TRY(hipMalloc(&d_gen_prev, n1 * 4));
+        HIP_TRY(hipMalloc(&d_sent_f, n1 * 8));
+        HIP_TRY(hipMalloc(&d_fstat, statb));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, fscan_tmp_bytes, FanoutCountIt(d_fcnt, FanoutCountCast()), d_rowptr_t,
+                                                 (int)n1, stream));
+        fscan_tmp_bytes = std::max<size_t>(fscan_tmp_bytes, 8);
+        HIP_TRY(hipMalloc(&d_fscan_tmp, fscan_tmp_bytes));
+        fanout_bytes = n1 * (4 + 4 + 8 + 4 + 4 + 8) + e1 * (4 + 1 + 4) + bw * 8 + statb + fscan_tmp_bytes;
+        device_bytes += fanout_bytes;
+        fanout_allocated = true;  // (only now: every buffer exists)
+    }
+    const size_t n1 = (size_t)n + 1;
+    HIP_TRY(hipMemsetAsync(d_fcnt, 0, n1 * 4, stream));      // (cnt[n] stays 0: rowptr_t[n] = the total)
+    HIP_TRY(hipMemsetAsync(d_rowptr_t, 0, n1 * 8, stream));  // the first tick pulls an empty frontier: all rows empty
+    HIP_TRY(hipMemsetAsync(d_recv_prev, 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_gen_prev, 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_sent_f, 0, n1 * 8, stream));
+    HIP_TRY(hipMemsetAsync(d_fstat, 0, (size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas * 8, stream));
+    HIP_TRY(hipMemcpyAsync(d_fthr, thr, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+    if (nnz) {
+        HIP_TRY(hipMemcpyAsync(d_in_thr, in_thr.data(), nnz * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_emult, em.data(), nnz, hipMemcpyHostToDevice, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));  // (the host arrays go out of scope)
+    fanout = true;
+    fanout_seed = seed;
+    return GOSSIP_OK;
+}
+
+// End of tick t: count pass (selection bitmap, per-node in-counts, sent), scan, compact pass -- all
+// on the engine stream, no host round trip.  The pull of t + 1 is launched after these.
+int gossip_engine::fanout_launch(int64_t t) {
+    gossip::FanoutArgs a;
+    a.rowptr = d_rowptr; a.col = d_col; a.in_thr = d_in_thr; a.emult = d_emult; a.thr = d_fthr;
+    a.recv = d_recv; a.gen = d_gen; a.recv_prev = d_recv_prev; a.gen_prev = d_gen_prev; a.sent_f = d_sent_f;
+    a.bitmap = d_fbitmap; a.cnt = d_fcnt; a.rowptr_t = d_rowptr_t; a.col_t = d_col_t; a.stat = d_fstat;
+    a.seed = fanout_seed; a.tick = (uint32_t)t; a.n = n;
+    const uint64_t nch = ((uint64_t)n + 63) / 64;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(
+        1, opt_fanout_grid > 0 ? (uint64_t)opt_fanout_grid : std::min<uint64_t>((nch + 3) / 4, 64ull * (uint64_t)num_cus));
+    const bool strided = gossip::launch_strides((uint64_t)grid * 4u, nch);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (cfg.flags & GOSSIP_F_TIMING) {
+        e0 = get_event();
+        e1 = get_event();
+        HIP_TRY(hipEventRecord(e0, stream));
+    }
+    HIP_TRY(hipMemsetAsync(d_fbitmap, 0, ((size_t)(nnz + 63) / 64 + 1) * 8, stream));
+    gossip::k_fanout_count<<<grid, 256, 0, stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    ledger.add(gossip::LK_FANOUT, 1u, strided);
+    size_t tmp = fscan_tmp_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_fscan_tmp, tmp, FanoutCountIt(d_fcnt, FanoutCountCast()), d_rowptr_t, (int)(n + 1),
+                                             stream));
+    gossip::k_fanout_compact<<<grid, 256, 0, stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    ledger.add(gossip::LK_FANOUT, 2u, strided);
+    if (e0) {
+        HIP_TRY(hipEventRecord(e1, stream));
+        timers_fanout.emplace_back(e0, e1);
+    }
+    fanout_launches++;
+    return GOSSIP_OK;
+}
+
 int gossip_engine::decode_trace(int64_t t) {
     HIP_TRY(hipStreamSynchronize(stream));
     if (hw == 0) return GOSSIP_OK;
@@ -3856,6 +4020,7 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
         e->opt_seen_fold = std::max<int64_t>(-1, std::min<int64_t>(1, env_option("GOSSIP_SEEN_FOLD", -1)));
         e->opt_reach_hops = std::max<int64_t>(2, std::min<int64_t>(1024, env_option("GOSSIP_REACH_HOPS", 32)));
         e->opt_reach_shares = env_option("GOSSIP_REACH_SHARES", 1) != 0 ? 1 : 0;
+        e->opt_fanout_grid = std::max<int64_t>(0, std::min<int64_t>(1ll << 24, env_option("GOSSIP_FANOUT_GRID", 0)));
         e->opt_reach_flush = std::max<int64_t>(1, std::min<int64_t>(gossip::kReachCap, env_option("GOSSIP_REACH_FLUSH", gossip::kReachCap)));
         // (GOSSIP_REACH=1 in the environment sets the flag for engines created without it: profiling
         //  an unchanged driver, tools/bench_reach.py)
@@ -3928,10 +4093,13 @@ static int set_graph(gossip_engine* e, uint32_t num_nodes, const int64_t* row_pt
             for (int64_t j = row_ptr[v]; j < row_ptr[v + 1]; j++) {
                 if (col[j] < 0 || (uint32_t)col[j] >= num_nodes) return set_error(GOSSIP_EINVAL, "col out of range");
                 p += mult ? mult[j] : 1u;
+                // (fanout mode draws per copy: the few entries that are not single links, by (row, col))
+                if (mult && mult[j] != 1u) e->h_multx.emplace_back(((uint64_t)v << 32) | (uint32_t)col[j], mult[j]);
             }
             e->h_peers[v] = p;
             e->h_sockets[v] = (uint32_t)(row_ptr[v + 1] - row_ptr[v]);
         }
+        std::sort(e->h_multx.begin(), e->h_multx.end());
         if (check_symmetry)
             if (int rc = check_symmetric(num_nodes, row_ptr, col)) return rc;
         // peer lists by degree (option peer_order), after the checks that name the caller's entries:
@@ -4233,6 +4401,7 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
     } else if (k == "young") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "young: -1 (auto), 0 or 1");
         if (e->have_sched) return set_error(GOSSIP_ESTATE, "young: set before the schedule");
+        if (value == 1 && e->fanout) return set_error(GOSSIP_EINVAL, "young: off in fanout mode (slots and hints are addressed by position in the full peer list)");
         e->opt_young = value;
     } else if (k == "young_age") {
         if (value < 1 || value > 64) return set_error(GOSSIP_EINVAL, "young_age: 1 .. 64 hops");
@@ -4273,9 +4442,12 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
         e->opt_young_nt = value;
     } else if (k == "young_idle") {
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "young_idle: 0 or 1");
+        if (value == 1 && e->fanout) return set_error(GOSSIP_EINVAL, "young_idle: off in fanout mode (no young tiles)");
+        e->forced_young_idle = value == 1;
         e->opt_young_idle = value;
     } else if (k == "pull_push") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "pull_push: -1 (auto), 0 or 1");
+        if (value == 1 && e->fanout) return set_error(GOSSIP_EINVAL, "pull_push: off in fanout mode (a writer marks its whole peer list, only the selected peers read it)");
         e->opt_pull_push = value;
     } else if (k == "peer_order") {
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "peer_order: 0 or 1");
@@ -4286,6 +4458,7 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
         e->opt_pull_batch = value;
     } else if (k == "young_skip") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "young_skip: -1 (auto), 0 or 1");
+        if (value == 1 && e->fanout) return set_error(GOSSIP_EINVAL, "young_skip: off in fanout mode (no young tiles)");
         e->opt_young_skip = value;
     } else if (k == "young_grid") {
         if (value < 0 || value > (1 << 20)) return set_error(GOSSIP_EINVAL, "young_grid: 0 .. 2^20 blocks");
@@ -4322,6 +4495,9 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "reach_shares: 0 or 1");
         if (e->have_sched) return set_error(GOSSIP_ESTATE, "reach_shares: set before the schedule");
         e->opt_reach_shares = value;
+    } else if (k == "fanout_grid") {
+        if (value < 0 || value > (1ll << 24)) return set_error(GOSSIP_EINVAL, "fanout_grid: 0 (auto) .. 2^24 blocks");
+        e->opt_fanout_grid = value;
     } else if (k == "reach_flush") {
         if (value < 1 || value > (int64_t)gossip::kReachCap) return set_error(GOSSIP_EINVAL, "reach_flush: 1 .. 255 rows");
         e->opt_reach_flush = value;
@@ -4346,7 +4522,8 @@ int gossip_engine_get_option(const gossip_engine* e, const char* name, int64_t* 
         {"dense_fused", e->opt_dense_fused}, {"dense_min_tiles", e->opt_dense_min_tiles},
         {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch},
         {"seen_fold", e->opt_seen_fold}, {"reach_hops", e->opt_reach_hops},
-        {"reach_shares", e->opt_reach_shares}, {"reach_flush", e->opt_reach_flush}};
+        {"reach_shares", e->opt_reach_shares}, {"reach_flush", e->opt_reach_flush},
+        {"fanout_grid", e->opt_fanout_grid}};
     for (const auto& o : opts)
         if (k == o.first) {
             *value = o.second;
@@ -4489,6 +4666,98 @@ int gossip_engine_set_link_timing(gossip_engine* e, int64_t ns_per_byte, uint32_
     return GOSSIP_OK;
 }
 
+// what fanout mode cannot run with, and where it may be set (both setters)
+static int fanout_check(gossip_engine* e) {
+    if (!e) return set_error(GOSSIP_EINVAL, "NULL engine");
+    if (!e->have_graph) return set_error(GOSSIP_ESTATE, "fanout: set the graph first");
+    if (e->have_sched) return set_error(GOSSIP_ESTATE, "fanout: set before the schedule");
+    if (e->batch)
+        return set_error(GOSSIP_EINVAL, "fanout: not with GOSSIP_F_HOP_BATCH (a batched tick is not the tick of the draw; hence no link timing)");
+    if (e->handshake) return set_error(GOSSIP_EINVAL, "fanout: not with GOSSIP_F_HANDSHAKE");
+    if (e->row_count > 1) return set_error(GOSSIP_EINVAL, "fanout: not with a row partition (one engine thins every row)");
+    if (e->cfg.mode == GOSSIP_MODE_DENSE)
+        return set_error(GOSSIP_EINVAL, "fanout: not in GOSSIP_MODE_DENSE (the adjacency contraction has no per-tick peer lists); use CSR or AUTO");
+    if (e->opt_young == 1 || e->opt_pull_push == 1 || e->opt_young_skip == 1 || e->forced_young_idle)
+        return set_error(GOSSIP_EINVAL, "fanout: options young, pull_push, young_skip and young_idle cannot be forced on "
+                                        "(they address side arrays by position in the full peer list)");
+    if (e->n >= 0x7fffffffu) return set_error(GOSSIP_EINVAL, "fanout: fewer than 2^31 - 1 nodes (the row-pointer scan counts n + 1 items in an int)");
+    if (e->tick0 < 0 || e->tick_end > (int64_t)0xffffffffll)
+        return set_error(GOSSIP_EINVAL, "fanout: ticks must fit 32 bits (the draw's counter word)");
+    return GOSSIP_OK;
+}
+
+static int fanout_set(gossip_engine* e, const uint32_t* thr, uint64_t seed) {
+    try {
+        if (int rc = e->fanout_setup(thr, seed)) return rc;
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+    if (e->dense) {  // AUTO had resolved to DENSE: fanout runs the CSR pull
+        e->dense = false;
+        hipFree(e->d_Ab);
+        e->d_Ab = nullptr;
+    }
+    return GOSSIP_OK;
+}
+
+int gossip_engine_set_forward_thresholds(gossip_engine* e, const uint32_t* thr, uint64_t seed) {
+    if (int rc = fanout_check(e)) return rc;
+    if (!thr) return set_error(GOSSIP_EINVAL, "NULL argument");
+    return fanout_set(e, thr, seed);
+}
+
+int gossip_engine_set_fanout(gossip_engine* e, uint32_t fanout, uint64_t seed) {
+    if (int rc = fanout_check(e)) return rc;
+    if (fanout < 1) return set_error(GOSSIP_EINVAL, "fanout >= 1");
+    try {
+        std::vector<uint32_t> thr(e->n);
+        for (uint32_t v = 0; v < e->n; v++) thr[v] = gossip::fanout_threshold(fanout, e->h_peers[v]);
+        return fanout_set(e, thr.data(), seed);
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+}
+
+int gossip_fanout_selected(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy, int64_t tick, uint32_t thr) {
+    return gossip::fanout_selected(seed, sender, receiver, copy, (uint32_t)tick, thr) ? 1 : 0;
+}
+
+int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* c) {
+    if (!e || !c) return set_error(GOSSIP_EINVAL, "NULL argument");
+    std::memset(c, 0, sizeof(*c));
+    if (!e->fanout) return GOSSIP_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    std::vector<unsigned long long> st((size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas);
+    HIP_TRY(hipMemcpy(st.data(), e->d_fstat, st.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < gossip::kFanoutStatReplicas; r++) {
+        c->selected_in += st[(size_t)r * gossip::kFanoutStatLine];
+        c->selected_out += st[(size_t)r * gossip::kFanoutStatLine + 1];
+    }
+    double ms = e->fanout_ms_done;
+    for (auto& p : e->timers_fanout) {
+        float x = 0.f;
+        HIP_TRY(hipEventElapsedTime(&x, p.first, p.second));
+        ms += x;
+        e->event_pool.push_back(p.first);
+        e->event_pool.push_back(p.second);
+    }
+    e->timers_fanout.clear();
+    e->fanout_ms_done = ms;
+    c->ms = ms;
+    c->launches = e->fanout_launches;
+    c->entries = e->fanout_launches * e->nnz;
+    // per tick: the count pass reads col, in_thr, emult per entry and writes a bit; per node it reads the
+    // row pointer, threshold, recv, gen and their copies and writes the copies, the count and (at most)
+    // sent; the scan reads a count and writes a pointer per node; the compact pass reads the bitmap and,
+    // per selected entry, reads col and writes col_t, plus two pointers per 64 nodes
+    const uint64_t n = e->n, nnz = e->nnz;
+    c->bytes = e->fanout_launches * (nnz * 9 + 2 * ((nnz + 63) / 64 + 1) * 8 + nnz / 8 + n * (8 + 4 + 16 + 8 + 4 + 16) + n * 12 +
+                                     (n + 63) / 64 * 16) +
+               c->selected_in * 8;
+    return GOSSIP_OK;
+}
+
 int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const gossip_gen_event* ev) {
     if (!e || (num_events && !ev)) return set_error(GOSSIP_EINVAL, "NULL argument");
     if (!e->have_graph) return set_error(GOSSIP_ESTATE, "set the graph first");
@@ -4537,6 +4806,24 @@ int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const goss
                                                     "window shares its id with another generation");
             }
         }
+        if (e->fanout && gossip::any_id_collision(e->ev.size(), e->ev.data())) {
+            // (GOSSIP_F_HOP_BATCH's rule: a generation of an already-processed id sends without a column,
+            //  which is exact only when every peer already holds the id -- not under a limited fanout)
+            std::vector<std::pair<uint32_t, size_t>> ids(e->ev.size());
+            for (size_t k = 0; k < e->ev.size(); k++) ids[k] = {e->ev[k].share_id, k};
+            std::sort(ids.begin(), ids.end());
+            size_t best = SIZE_MAX, other = 0;
+            for (size_t k = 1; k < ids.size(); k++)
+                if (ids[k].first == ids[k - 1].first && ids[k].second < best) {
+                    best = ids[k].second;  // (the later event of the pair, earliest in time order)
+                    other = ids[k - 1].second;
+                }
+            const gossip_gen_event &x = e->ev[best], &y = e->ev[other];
+            return set_error(GOSSIP_EINVAL, "fanout needs unique share ids: id " + std::to_string(x.share_id) + " of node " +
+                                                std::to_string(x.node) + " at " + std::to_string(x.ns) + " ns was generated by node " +
+                                                std::to_string(y.node) + " at " + std::to_string(y.ns) +
+                                                " ns before (renumber the ids: gossip.unique_ids, gossip_sim --uniqueIds)");
+        }
         if (e->batch) {
             // Shares are independent floods when no two generations share an id (the seen set
             // is keyed by id, p2pnode.cc:189), so each can run at any tick: generation g of a
@@ -4577,7 +4864,7 @@ int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const goss
             const bool coll = e->comp.empty() && gossip::any_id_collision(e->ev.size(), e->ev.data());
             const bool may_young = !e->dense && !e->batch && !e->handshake && e->row_count == 1 &&
                                    e->opt_rehearse_rows <= 1 && !(e->cfg.flags & GOSSIP_F_NOSKIP) &&
-                                   e->n < (1u << 31) &&
+                                   e->n < (1u << 31) && !e->fanout &&
                                    (e->opt_young == 1 || (e->opt_young == -1 && e->n >= (1u << 20)));
             std::lock_guard<std::mutex> g(g_derived_mu);
             e->graph_derived(coll, e->cfg.max_words == 0, may_young);
@@ -4685,7 +4972,9 @@ int gossip_engine_get_stats(gossip_engine* e, uint32_t* gen, uint32_t* recv, uin
     HIP_TRY(hipMemcpy(r.data(), e->d_recv, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(g.data(), e->d_gen, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(eg.data(), e->d_effgen, n * 4, hipMemcpyDeviceToHost));
-    if (sent) {  // births' sends + deg x recv (header comment)
+    if (sent && e->fanout) {  // the selected Sends, counted tick by tick (k_fanout_count)
+        HIP_TRY(hipMemcpy(sent, e->d_sent_f, n * 8, hipMemcpyDeviceToHost));
+    } else if (sent) {  // births' sends + deg x recv (header comment)
         HIP_TRY(hipMemcpy(sent, e->d_sent, n * 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) sent[i] += (uint64_t)r[i] * e->h_peers[i];
     }
@@ -4758,7 +5047,10 @@ int gossip_engine_get_counters(gossip_engine* e, gossip_counters* c) {
     e->pull_ms_done = ms;
     c->pull_ms = ms;
     HIP_TRY(hipMemsetAsync(e->d_scalars, 0, 16, e->stream));
-    k_sum_sent<<<256, 256, 0, e->stream>>>(e->d_sent, e->d_recv, e->d_deg, e->n, e->d_scalars);
+    if (e->fanout)
+        gossip::k_sum_u64<<<256, 256, 0, e->stream>>>(e->d_sent_f, e->n, e->d_scalars);
+    else
+        k_sum_sent<<<256, 256, 0, e->stream>>>(e->d_sent, e->d_recv, e->d_deg, e->n, e->d_scalars);
     k_sum_u32<<<256, 256, 0, e->stream>>>(e->d_recv, nullptr, e->n, e->d_scalars + 1);
     HIP_TRY(hipGetLastError());
     unsigned long long v[2];
@@ -4963,6 +5255,15 @@ int gossip_engine_reset_timing(gossip_engine* e) {
     for (auto& p : e->timers_reach_slots) e->event_pool.push_back(p.first);
     e->timers_reach_slots.clear();
     e->reach_slots_ms_done = 0.0;
+    for (auto& p : e->timers_fanout) {
+        e->event_pool.push_back(p.first);
+        e->event_pool.push_back(p.second);
+    }
+    e->timers_fanout.clear();
+    e->fanout_ms_done = 0.0;
+    e->fanout_launches = 0;
+    if (e->d_fstat)
+        HIP_TRY(hipMemsetAsync(e->d_fstat, 0, (size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas * 8, e->stream));
     if (e->d_rbytes) HIP_TRY(hipMemsetAsync(e->d_rbytes, 0, 8, e->stream));
     if (e->d_phase_ts) HIP_TRY(hipMemsetAsync(e->d_phase_ts + 2, 0, 16, e->stream));
     e->rehearse_harvest();  // (row-partition rehearsal: restart the per-range sums)

@@ -57,6 +57,9 @@ struct Options {
     double memLimitMB = 0;             // device memory budget per engine (0: the device's)
     std::string schedule = "exact";    // exact (the reference's mt19937 stream) | philox (GPU)
     std::string reach;                 // reach profile per counted event (GOSSIP_F_REACH)
+    uint32_t fanout = 0;               // fanout-limited gossip: expected fanout (0: the reference's flood)
+    uint64_t fanoutSeed = 1;           // ... and the seed of its per-(link, tick) draws
+    bool uniqueIds = false;            // renumber share ids 1..len in event order (ids are only seen-set keys)
 };
 
 void usage() {
@@ -69,7 +72,8 @@ void usage() {
                  "                  [--mode=auto|csr|dense] [--dumpLinks=F] [--dumpEvents=F]\n"
                  "                  [--links=F] [--events=F] [--dumpTrace=F] [--netanim=F] [--noPackets]\n"
                  "                  [--log=F|-] [--gpus=N] [--shards=S] [--layout=shards|rows]\n"
-                 "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n");
+                 "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n"
+                 "                  [--fanout=K] [--fanoutSeed=S] [--uniqueIds]\n");
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -139,6 +143,18 @@ bool parse(int argc, char** argv, Options& o) {
         else if (key == "memLimitMB") { if (!num(o.memLimitMB) || o.memLimitMB < 0) return false; }
         else if (key == "schedule") { if (!need()) return false; o.schedule = val; }
         else if (key == "reach") { if (!need()) return false; o.reach = val; }
+        else if (key == "fanout") { if (!num(d) || d < 1 || d > 4294967295.0) return false; o.fanout = (uint32_t)d; }
+        else if (key == "fanoutSeed") {
+            if (!need()) return false;
+            char* end = nullptr;
+            errno = 0;
+            o.fanoutSeed = std::strtoull(val.c_str(), &end, 0);
+            if (errno || end == val.c_str() || *end) {
+                std::fprintf(stderr, "invalid value '%s' for --fanoutSeed\n", val.c_str());
+                return false;
+            }
+        }
+        else if (key == "uniqueIds") o.uniqueIds = true;
         else {
             std::fprintf(stderr, "unknown option --%s\n", key.c_str());
             return false;
@@ -209,7 +225,7 @@ struct RowGroup {
 void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank, uint32_t count,
                 const uint8_t* uid, RowGroup* group, const gossip_topology* topo, const gossip_schedule* sched,
                 const std::vector<double>& per_t, bool link_timing, bool want_trace, double mem_limit_mb,
-                Part& out) {
+                uint32_t fanout, uint64_t fanout_seed, Part& out) {
     gossip_config cfg = base;
     cfg.device = device;
     if (!rows && count > 1) {
@@ -234,6 +250,7 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
     // NS-3 link timing: 5 Mbps DataRate (p2pnetwork.cc:113) = 1600 ns/byte, 54 header bytes
     // (PPP + IPv4 + TCP with timestamps), 1 ns TcpSocketBase send deferral (gossip.h)
     if (link_timing && (rc = gossip_engine_set_link_timing(eng, 1600, 54, 1))) return fail("link timing", rc);
+    if (fanout && (rc = gossip_engine_set_fanout(eng, fanout, fanout_seed))) return fail("fanout", rc);
     for (double t : per_t)  // Start(): p2pnetwork.cc:201-204
         if ((rc = gossip_engine_add_snapshot(eng, gossip_seconds_to_ns(t)))) return fail("snapshot", rc);
     if ((rc = gossip_engine_set_schedule_obj(eng, sched))) return fail("engine schedule", rc);
@@ -323,6 +340,14 @@ int main(int argc, char** argv) {
     } else if (gossip_schedule_create(n, o.nodeSeed, t_start, t_cut, 0, 0, o.threads, &sched)) {
         return die("schedule");
     }
+    if (o.uniqueIds) {  // ids 1..len in event order: the modes that need unique ids (--fanout, --hopBatch) at any n
+        std::vector<gossip_gen_event> ev(gossip_schedule_size(sched));
+        if (!ev.empty()) gossip_schedule_get(sched, ev.data());
+        for (size_t k = 0; k < ev.size(); k++) ev[k].share_id = (uint32_t)(k + 1);
+        gossip_schedule_destroy(sched);
+        sched = nullptr;
+        if (gossip_schedule_from_events(ev.size(), ev.data(), &sched)) return die("schedule renumbering");
+    }
     if (!o.dumpLinks.empty()) {
         std::vector<uint32_t> a(gossip_topology_num_links(topo)), b(a.size());
         gossip_topology_get_links(topo, a.data(), b.data());
@@ -389,7 +414,7 @@ int main(int argc, char** argv) {
                 // device g runs shards g, g + N, ... (rows: exactly rank g)
                 for (uint32_t r = g; r < count; r += ng)
                     run_engine(cfg, o.device + (int)g, rows, r, count, uid.data(), gp, topo, sched, per_t,
-                               o.linkTiming, want_trace, o.memLimitMB, parts[r]);
+                               o.linkTiming, want_trace, o.memLimitMB, o.fanout, o.fanoutSeed, parts[r]);
             });
         for (auto& t : th) t.join();
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
@@ -405,6 +430,8 @@ int main(int argc, char** argv) {
             continue;
         }
         std::fprintf(stderr, "gossip_sim: %s\n", err.c_str());
+        if (o.fanout && !o.uniqueIds && err.find("unique share ids") != std::string::npos)
+            std::fprintf(stderr, "gossip_sim: --fanout needs unique share ids: add --uniqueIds to renumber them\n");
         return 1;
     }
     if (o.hopBatch)

@@ -15,8 +15,8 @@
 namespace gossip {
 
 // kernels the ledger records (gossip.h: GOSSIP_K_*)
-enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4, LK_REACH = 5 };
-constexpr uint32_t kLaunchKernels = 6;
+enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4, LK_REACH = 5, LK_FANOUT = 6 };
+constexpr uint32_t kLaunchKernels = 7;
 
 // k_pull's template flags (gossip.h: GOSSIP_PULL_*)
 enum : uint32_t { PK_NT = 1u, PK_SP = 2u, PK_PUSH = 4u, PK_SHORT = 8u, PK_FOLD = 16u };
@@ -82,7 +82,8 @@ constexpr bool dense_split_has_empty(uint32_t nst, uint32_t ksplit) {
 
 struct LaunchRecord {
     uint32_t kernel;   // LaunchKernel
-    uint32_t variant;  // k_pull: pull_key; k_pull_young: its bool template argument; k_dense_bits: ksplit; else 0
+    uint32_t variant;  // k_pull: pull_key; k_pull_young: its bool template argument; k_dense_bits: ksplit;
+                       // k_fanout: 1 the count pass, 2 the compact pass; else 0
     uint64_t launches;
     uint64_t strided;
 };

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "philox.h"
 
 using gossip::set_error;
 
@@ -43,21 +44,7 @@ namespace {
 
 constexpr uint32_t kKey1 = 0x53484152u;  // "SHAR": second key word of the schedule stream
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = (uint32_t)p1;
-        c[2] = n2;
-        c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+using gossip::philox4x32_10;  // (philox.h: shared with the fanout selection)
 
 // ns-3 Seconds(x): round-half-up(x * 1e9) computed exactly (host twin: exact_scale_round).
 __device__ int64_t seconds_to_ns_exact(double x) {

@@ -63,10 +63,13 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_abort", "gossip_engine_get_rehearsal", "gossip_engine_get_rehearsal_peak",
     "gossip_engine_get_option", "gossip_engine_get_launches", "gossip_pull_instantiations",
     "gossip_engine_get_reach_totals", "gossip_engine_get_reach",
+    "gossip_engine_set_fanout", "gossip_engine_set_forward_thresholds", "gossip_fanout_selected",
+    "gossip_engine_get_fanout_counters",
 )
 
 # launch ledger (gossip.h): kernel ids and k_pull's template flags
-K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP, K_REACH = range(6)
+K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP, K_REACH, K_FANOUT = range(7)
+FANOUT_ALWAYS = 0xFFFFFFFF  # forward threshold: probability 1
 PULL_NT, PULL_SP, PULL_PUSH, PULL_SHORT, PULL_FOLD = 1, 2, 4, 8, 16
 
 # NS-3 5 Mbps point-to-point links (p2pnetwork.cc:113): ns per byte, PPP+IPv4+TCP(timestamp
@@ -126,6 +129,13 @@ class gossip_counters(C.Structure):
         ("young_idle_ticks", C.c_uint64), ("pull_fold_rows", C.c_uint64),
         ("reach_launches", C.c_uint64), ("reach_ms", C.c_double), ("reach_bytes", C.c_uint64),
         ("reach_slots_ms", C.c_double),
+    ]
+
+
+class gossip_fanout_counters(C.Structure):
+    _fields_ = [
+        ("launches", C.c_uint64), ("selected_in", C.c_uint64), ("selected_out", C.c_uint64),
+        ("entries", C.c_uint64), ("ms", C.c_double), ("bytes", C.c_uint64),
     ]
 
 
@@ -250,6 +260,10 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_get_trace": (C.c_int, [P, P, P, P, P, P]),
         "gossip_engine_get_reach_totals": (C.c_int, [P, u32, P, C.POINTER(u32)]),
         "gossip_engine_get_reach": (C.c_int, [P, u64, u64, P]),
+        "gossip_engine_set_fanout": (C.c_int, [P, u32, u64]),
+        "gossip_engine_set_forward_thresholds": (C.c_int, [P, P, u64]),
+        "gossip_fanout_selected": (C.c_int, [u64, u32, u32, u32, i64, u32]),
+        "gossip_engine_get_fanout_counters": (C.c_int, [P, C.POINTER(gossip_fanout_counters)]),
         "gossip_engine_destroy": (None, [P]),
         "gossip_format_statistics": (i64, [u32, P, P, P, P, P, P, P, C.c_char_p, u64]),
         "gossip_format_periodic": (i64, [C.c_double, u32, u64, u64, u64, C.c_char_p, u64]),
@@ -430,6 +444,24 @@ def shard_events(topo: "Topology", ev: np.ndarray, shard_count: int, by_tick_lat
     return owner
 
 
+def fanout_selected(seed: int, sender: int, receiver: int, copy: int, tick: int, thr: int) -> bool:
+    """The fanout selection rule (gossip.h, gossip_fanout_selected): is the Send sender -> receiver,
+    copy `copy`, of tick `tick` made under the sender's threshold `thr`?  No engine, no device."""
+    return bool(load_library().gossip_fanout_selected(int(seed), int(sender), int(receiver), int(copy), int(tick),
+                                                      int(thr)))
+
+
+def unique_ids(ev: np.ndarray) -> np.ndarray:
+    """A copy of the events with share ids renumbered 1..len in event order.  Ids are only seen-set
+    keys, so a schedule whose ids collide (n > 128,849) runs in the modes that need unique ids
+    (fanout, F_HOP_BATCH) after this."""
+    out = np.array(ev, dtype=GEN_EVENT_DTYPE, copy=True)
+    if out.size >= 1 << 32:
+        raise GossipError("unique_ids: more than 2^32 - 1 events", E_INVAL)
+    out["share_id"] = np.arange(1, out.size + 1, dtype=np.uint32)
+    return out
+
+
 def events_from_arrays(ns, node, share_id) -> np.ndarray:
     ev = np.empty(len(ns), GEN_EVENT_DTYPE)
     ev["ns"] = ns
@@ -550,6 +582,25 @@ class Engine:
     def set_link_timing(self, ns_per_byte: int, header_bytes: int, send_defer_ns: int):
         _check(load_library().gossip_engine_set_link_timing(
             self._h, int(ns_per_byte), int(header_bytes), int(send_defer_ns)), "link timing")
+
+    def set_fanout(self, k: int, seed: int = 1):
+        """Fanout-limited gossip with an expected fanout of k (gossip.h, gossip_engine_set_fanout):
+        after the graph, before the schedule."""
+        _check(load_library().gossip_engine_set_fanout(self._h, int(k), int(seed)), "set fanout")
+
+    def set_forward_thresholds(self, thr, seed: int = 1):
+        """Fanout-limited gossip with per-node forward thresholds (probability thr / 2^32,
+        0xffffffff = always); after the graph, before the schedule."""
+        thr = np.ascontiguousarray(thr, np.uint32)
+        if thr.size != self.n:
+            raise GossipError("set_forward_thresholds: one threshold per node", E_INVAL)
+        _check(load_library().gossip_engine_set_forward_thresholds(self._h, _vp(thr), int(seed)),
+               "set forward thresholds")
+
+    def fanout_counters(self) -> gossip_fanout_counters:
+        c = gossip_fanout_counters()
+        _check(load_library().gossip_engine_get_fanout_counters(self._h, C.byref(c)), "fanout counters")
+        return c
 
     def set_schedule(self, ev: np.ndarray):
         ev = np.ascontiguousarray(ev, GEN_EVENT_DTYPE)
