@@ -48,6 +48,7 @@
 
 #include "internal.h"
 #include "pull_plan.h"
+#include "row_msg.h"
 #include "launch_ledger.h"
 #include "reach_kernel.h"
 #include "fanout_kernel.h"
@@ -57,6 +58,9 @@ using gossip::PullShape;
 using gossip::PullWindow;
 using gossip::TickPlan;
 using gossip::pull_shape;
+using gossip::RowChunk;
+using gossip::RowMsgLayout;
+using gossip::row_msg_layout;
 
 namespace {
 
@@ -1059,9 +1063,11 @@ struct gossip_engine {
     int tick_step_a(int64_t t);  // up to the tick's kernels (pull, births, snapshot counts)
     int tick_step_b(int64_t t);  // exchange (RCCL) + liveness read-back + bookkeeping
     int exchange_rccl(int64_t t);
-    // compressed row exchange (row partition): message buffers and traffic counters
-    int pack_rows(int64_t t, uint32_t c, hipStream_t s);
-    int unpack_rows(int64_t t, uint32_t r, uint32_t c, const uint64_t* msg, uint64_t words, hipStream_t s);
+    // compressed row exchange (row partition, row_msg.h): message buffers and traffic counters
+    enum class MsgRoom { kExact, kWorstCase };  // pack_msg: how d_msg is sized
+    int pack_msg(int64_t t, const RowChunk& ch, MsgRoom room, hipStream_t s);
+    int unpack_msg(int64_t t, const RowChunk& ch, const uint64_t* msg, const uint64_t* rows, uint64_t r0,
+                   uint64_t r1, bool prefix, hipStream_t s);
     int ensure_dev(uint64_t*& p, uint64_t& cap, uint64_t words, uint64_t preserve = 0);
     uint64_t* d_msg = nullptr;       // this rank's packed message
     uint64_t msg_cap = 0, msg_words = 0;
@@ -1076,16 +1082,16 @@ struct gossip_engine {
     // every rank derives from the same all-gathered row counts, so each broadcast's length is known
     // without reading the message first; rows beyond it go in a second round after the tick's one
     // host wait.
-    std::vector<uint64_t> xcap;          // [r * kMaxChunks + c] rows
+    std::vector<uint64_t> xcap;          // [r * kMaxChunks + c] rows: read through xcap_at
+    uint64_t& xcap_at(uint32_t r, uint32_t c) {  // (sized at first use, all zero)
+        if (xcap.size() != (size_t)row_count * kMaxChunks) xcap.assign((size_t)row_count * kMaxChunks, 0ull);
+        return xcap[(size_t)r * kMaxChunks + c];
+    }
     uint64_t* d_tot = nullptr;           // all-gathered row counts of the tick [c * row_count + r]
     uint64_t* h_tot = nullptr;           // pinned copy
     uint64_t* d_ovf = nullptr;           // overflow rows received in the second round
     uint64_t ovf_cap = 0;
     bool xchunks_checked = false;
-    uint64_t x_overflow_rounds = 0;      // (rank, chunk) messages that needed a second round
-    int pack_dev(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, hipStream_t s);
-    int unpack_dev(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, const uint64_t* msg, const uint64_t* rows,
-                   uint64_t r0, uint64_t r1, bool prefix, hipStream_t s);
     uint64_t sizes_cap = 0;
     std::atomic<bool> aborted{false};  // gossip_engine_abort: comm torn down by another thread
     std::atomic<int> comm_issuing{0};  // collectives being issued on comm right now (COMM_TRY)
@@ -1096,7 +1102,7 @@ struct gossip_engine {
     // ev_chunk[c]; chunk c's message is packed, sent and the other ranks' chunk c unpacked on
     // xstream while the engine stream computes chunk c + 1.  Every rank uses the same chunk
     // count (checked by the RCCL backend).  kWholeRows = one message of all own rows.
-    static constexpr uint32_t kMaxChunks = 16, kWholeRows = 0xffffffffu;
+    static constexpr uint32_t kMaxChunks = 16, kWholeRows = gossip::kWholeRows;
     int64_t opt_xchunks = 4;
     uint32_t nchunks = 1;            // chunks of the current tick
     hipStream_t xstream = nullptr;
@@ -1104,7 +1110,10 @@ struct gossip_engine {
     hipEvent_t ev_xdone = nullptr;
     int64_t packed_tick = -1;        // host-staged export: message of (tick, chunk) already packed
     uint32_t packed_chunk = 0;
-    void chunk_rows(uint32_t r, uint32_t c, uint64_t* lo, uint64_t* hi) const;
+    RowChunk chunk_rows(uint32_t r, uint32_t c) const {  // rank r's chunk c of this tick (row_msg.h)
+        return gossip::row_msg_chunk(row_lo[r], row_lo[r + 1], nchunks, c, hw);
+    }
+    RowMsgLayout chunk_layout(const RowChunk& ch) const { return row_msg_layout(ch.hi - ch.lo, ntw, ch.wlive); }
     TickPlan plan;  // this tick's (pull_plan.h): reset by tick_step_a, filled by its stages
     // tick_step_a's stages, in order; each fills its part of the tick's plan (TickPlan)
     int stage_births(TickPlan& p);
@@ -1125,9 +1134,6 @@ struct gossip_engine {
     int launch_young(const TickPlan& p, const PullArgs& a, hipStream_t ys);
     void run_dedup(const PullArgs& base);
     int run_dense(uint64_t lo, uint64_t hi, const unsigned long long* live_prev);
-    int pack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, hipStream_t s);
-    int unpack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, const uint64_t* msg, uint64_t words,
-                     hipStream_t s);
     // Row-partition rehearsal (option rehearse_rows = R, one unpartitioned CSR engine): the pull
     // runs as R row-range launches, and every range's F_next rows go through the real pack and
     // unpack kernels (into the same rows: idempotent), each step timed per range -- one rank's
@@ -2233,7 +2239,11 @@ void gossip_engine::group_births_by_chunk(TickPlan& p) {
     cb_off[1] = nb;
     if (nchunks > 1) {
         uint64_t clo[kMaxChunks + 1];
-        for (uint32_t c = 0; c < nchunks; c++) chunk_rows(row_rank, c, &clo[c], &clo[c + 1]);
+        for (uint32_t c = 0; c < nchunks; c++) {
+            const RowChunk ch = chunk_rows(row_rank, c);
+            clo[c] = ch.lo;
+            clo[c + 1] = ch.hi;
+        }
         auto chunk_of = [&](uint32_t v) {
             uint32_t c = 0;
             while (c + 1 < nchunks && v >= clo[c + 1]) c++;
@@ -2831,8 +2841,8 @@ int gossip_engine::launch_tick(TickPlan& p) {
             // without chunks: the MFMA contraction (DENSE) or the pull (CSR), summed over chunks.
             const bool timing = (cfg.flags & GOSSIP_F_TIMING) != 0;
             for (uint32_t c = 0; c < nchunks; c++) {
-                uint64_t lo, hi;
-                chunk_rows(row_rank, c, &lo, &hi);
+                const RowChunk ch = chunk_rows(row_rank, c);
+                const uint64_t lo = ch.lo, hi = ch.hi;
                 if (hi > lo) {  // (chunk 0 never is empty: a rank owns >= 512 rows)
                     hipEvent_t c0 = timing ? (c ? get_event() : e0) : nullptr;
                     hipEvent_t c1 = timing ? (c ? get_event() : e1) : nullptr;
@@ -2992,50 +3002,14 @@ int gossip_engine::launch_tick(TickPlan& p) {
 }
 
 // ---- compressed row exchange (row partition) --------------------------------------------
-// A rank's message for tick t and row chunk c: its rows [lo, hi) of F_next (the chunk, or all
-// its rows), restricted to OCCUPIED 16-word tile rows (the nz bits; unoccupied rows hold stale
-// words no reader loads), plus -- in its last chunk only -- its partial liveness.  Layout in
-// uint64 words:
-//   [0]                      number of rows R
-//   [1, 1 + m)               nz words of rows lo..hi-1 (m = (hi - lo) * ntw)
-//   [.., + ceil((k+1)/2))    uint32 row offsets: rows of node lo+i start at offset[i] (k = hi-lo)
-//   [.., + 16 R)             the rows, node by node, tile by tile
-//   [.., + wact)             liveness words of this rank's rows (last chunk / whole rows)
-// The receiver knows k and whether liveness is present from (rank, chunk), so R follows from
-// the message size: no header read-back.
-
-// Rows of rank r's chunk c: 512-row blocks (the dense tile and the row-partition granule), the
-// last chunks possibly empty; kWholeRows = all of rank r's rows.
-void gossip_engine::chunk_rows(uint32_t r, uint32_t c, uint64_t* lo, uint64_t* hi) const {
-    const uint64_t a = row_lo[r], b = row_lo[r + 1];
-    if (c == kWholeRows || nchunks <= 1) {
-        *lo = a;
-        *hi = b;
-        return;
-    }
-    const uint64_t per = ((b - a + nchunks - 1) / nchunks + 511) / 512 * 512;
-    *lo = std::min<uint64_t>(b, a + (uint64_t)c * per);
-    *hi = std::min<uint64_t>(b, *lo + per);
-}
+// The message, its chunk geometry and the broadcast capacities: row_msg.h.
+static_assert(gossip::kRowMsgRowWords == kTileWords, "a message row is one tile row");
 
 int gossip_engine::ensure_xstream() {
     if (xstream) return GOSSIP_OK;
     HIP_TRY(hipStreamCreateWithFlags(&xstream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&ev_xdone, hipEventDisableTiming));
     return GOSSIP_OK;
-}
-
-struct PackLayout {
-    uint64_t nz, off, rows, live, total;
-};
-PackLayout pack_layout(uint64_t k, uint32_t ntw, uint64_t nrows, uint32_t wact) {
-    PackLayout L;
-    L.nz = 1;
-    L.off = L.nz + k * ntw;
-    L.rows = L.off + (k + 2) / 2;
-    L.live = L.rows + 16 * nrows;
-    L.total = L.live + wact;
-    return L;
 }
 
 // per node: number of occupied tile rows; nz words copied into the message
@@ -3103,20 +3077,6 @@ __global__ void k_or_words(const uint64_t* __restrict__ src, uint32_t n, unsigne
 // on the device: no host wait per chunk)
 __global__ void k_msg_header(const uint32_t* __restrict__ off_end, uint64_t* __restrict__ hdr) { *hdr = *off_end; }
 
-// RCCL message layout: a fixed prefix (header, occupancy words, row offsets, liveness) whose size
-// every rank knows, then the rows; a broadcast carries the prefix and up to `cap` rows
-struct DevLayout {
-    uint64_t nz, off, live, rows;  // rows = prefix words
-};
-DevLayout dev_layout(uint64_t k, uint32_t ntw, uint32_t wlive) {
-    DevLayout L;
-    L.nz = 1;
-    L.off = L.nz + k * ntw;
-    L.live = L.off + (k + 2) / 2;
-    L.rows = L.live + wlive;
-    return L;
-}
-
 #define NCCL_TRY(x)                                                                         \
     do {                                                                                    \
         ncclResult_t r_ = (x);                                                              \
@@ -3171,20 +3131,18 @@ int gossip_engine::ensure_dev(uint64_t*& p, uint64_t& cap, uint64_t words, uint6
     return GOSSIP_OK;
 }
 
-// Pack this rank's rows of chunk c of F_next (after the chunk's pull and births) into d_msg on
-// stream s; msg_words = size.  (One host wait: the row count sizes the message.)
-int gossip_engine::pack_rows(int64_t t, uint32_t c, hipStream_t s) {
-    uint64_t lo, hi;
-    chunk_rows(row_rank, c, &lo, &hi);
-    const uint32_t wlive = (c == kWholeRows || c + 1 >= nchunks) ? hw : 0u;  // liveness: last chunk
-    return pack_range(t, lo, hi, wlive, s);
-}
-
-// Pack rows [lo, hi) of F_next (+ `wlive` liveness words) into d_msg on stream s.
-int gossip_engine::pack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, hipStream_t s) {
+// Pack rows ch of F_next (after their pull and births) and ch.wlive liveness words into d_msg on
+// stream s; the header (the row count) is written on the device.
+// kWorstCase (RCCL, lockstep): d_msg holds every tile row of the range -- no host wait.
+// kExact (host-staged, rehearsal: memory is tight there, and the rehearsal reports the buffer a
+// rank needs): ONE host wait reads the row count, d_msg grows to the message's size keeping the
+// prefix, and msg_words is set.
+int gossip_engine::pack_msg(int64_t t, const RowChunk& ch, MsgRoom room, hipStream_t s) {
     const int nxt = fcur ^ 1, lv = (int)(t % 3);
-    const uint64_t k = hi - lo;
-    int rc = ensure_dev(d_msg, msg_cap, pack_layout(k, ntw, 0, wlive).rows);
+    const uint64_t lo = ch.lo, k = ch.hi - ch.lo;
+    const RowMsgLayout L = chunk_layout(ch);
+    const bool exact = room == MsgRoom::kExact;
+    int rc = ensure_dev(d_msg, msg_cap, L.total_words(exact ? 0 : gossip::row_msg_worst_rows(k, hw)));
     if (rc) return rc;
     if (k + 1 > cnt_cap) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -3192,76 +3150,62 @@ int gossip_engine::pack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wliv
         cnt_cap = k + 1;
         HIP_TRY(hipMalloc(&d_cnt, cnt_cap * 4));
     }
-    const PackLayout L0 = pack_layout(k, ntw, 0, wlive);
-    uint32_t* off = reinterpret_cast<uint32_t*>(d_msg + L0.off);
-    k_pack_count<<<(uint32_t)((k + 1 + 255) / 256), 256, 0, s>>>(d_nz[nxt] + lo * ntw, k, ntw, d_msg + L0.nz, d_cnt);
+    uint32_t* off = reinterpret_cast<uint32_t*>(d_msg + L.off);
+    k_pack_count<<<(uint32_t)((k + 1 + 255) / 256), 256, 0, s>>>(d_nz[nxt] + lo * ntw, k, ntw, d_msg + L.nz, d_cnt);
     HIP_TRY(hipGetLastError());
     size_t tmp = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_cnt, off, (int)(k + 1), s));
-    if (tmp > scan_tmp_bytes) {
+    if (tmp > scan_tmp_bytes) {  // (first use of a chunk size only)
         HIP_TRY(hipStreamSynchronize(s));
         hipFree(d_scan_tmp);
         scan_tmp_bytes = tmp;
         HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
     }
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, tmp, d_cnt, off, (int)(k + 1), s));
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, off + k, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const PackLayout L = pack_layout(k, ntw, total, wlive);
-    // (the layout's header parts do not depend on the row count: grow keeping them; through
-    // ensure_dev, so the growth counts in device_bytes and respects mem_limit)
-    if (L.total > msg_cap) {
-        if ((rc = ensure_dev(d_msg, msg_cap, L.total, L.rows))) return rc;
+    k_msg_header<<<1, 1, 0, s>>>(off + k, d_msg);
+    bool any_rows = true;  // (unknown without the wait)
+    if (exact) {
+        uint32_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, off + k, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // (through ensure_dev, so the growth counts in device_bytes and respects mem_limit)
+        if ((rc = ensure_dev(d_msg, msg_cap, L.total_words(total), L.rows))) return rc;
         off = reinterpret_cast<uint32_t*>(d_msg + L.off);
+        any_rows = total != 0;
+        msg_words = L.total_words(total);
+        exchange_bytes_out += msg_words * 8;
     }
-    const unsigned long long hdr = total;
-    HIP_TRY(hipMemcpyAsync(d_msg, &hdr, 8, hipMemcpyHostToDevice, s));
-    if (total) {
+    if (any_rows) {
         const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((k + 3) / 4, 4096));
         k_move_rows<true><<<g, 256, 0, s>>>(d_F[nxt], stride, lo, k, d_msg + L.nz, ntw, off, d_msg + L.rows);
-        HIP_TRY(hipGetLastError());
     }
-    if (wlive) HIP_TRY(hipMemcpyAsync(d_msg + L.live, d_live[lv], (size_t)wlive * 8, hipMemcpyDeviceToDevice, s));
-    msg_words = L.total;
-    exchange_bytes_out += L.total * 8;
+    HIP_TRY(hipGetLastError());
+    if (ch.wlive) HIP_TRY(hipMemcpyAsync(d_msg + L.live, d_live[lv], (size_t)ch.wlive * 8, hipMemcpyDeviceToDevice, s));
     return GOSSIP_OK;
 }
 
-// Unpack rank r's message of chunk c (device buffer, `words` long) into this engine's F_next,
-// nz_next and (last chunk) liveness, on stream s.  No host wait.
-int gossip_engine::unpack_rows(int64_t t, uint32_t r, uint32_t c, const uint64_t* msg, uint64_t words, hipStream_t s) {
-    uint64_t lo, hi;
-    chunk_rows(r, c, &lo, &hi);
-    const uint32_t wlive = (c == kWholeRows || c + 1 >= nchunks) ? hw : 0u;
-    const PackLayout L0 = pack_layout(hi - lo, ntw, 0, wlive);
-    if (words < L0.total || (words - L0.total) % 16u)
-        return set_error(GOSSIP_EINVAL, "row exchange: message of rank " + std::to_string(r) +
-                                            " has the wrong size (ranks diverged?)");
-    return unpack_range(t, lo, hi, wlive, msg, words, s);
-}
-
-// Unpack a message of rows [lo, hi) (+ `wlive` liveness words) into F_next / nz_next / liveness.
-int gossip_engine::unpack_range(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, const uint64_t* msg,
-                                uint64_t words, hipStream_t s) {
+// Unpack message rows [r0, r1) of another rank's rows ch into F_next: `msg` is the message's prefix,
+// `rows` points at message row r0.  prefix: the first (or only) round -- also the occupancy words
+// into nz_next and the liveness words ORed into the tick's, and r1 capped by the header's row
+// count on the device.  No host wait.
+int gossip_engine::unpack_msg(int64_t t, const RowChunk& ch, const uint64_t* msg, const uint64_t* rows, uint64_t r0,
+                              uint64_t r1, bool prefix, hipStream_t s) {
     const int nxt = fcur ^ 1, lv = (int)(t % 3);
-    const uint64_t k = hi - lo;
-    const PackLayout L0 = pack_layout(k, ntw, 0, wlive);
-    const uint64_t total = (words - L0.total) / 16u;
-    const PackLayout L = pack_layout(k, ntw, total, wlive);
-    if (k) HIP_TRY(hipMemcpyAsync(d_nz[nxt] + lo * ntw, msg + L.nz, (size_t)k * ntw * 8, hipMemcpyDeviceToDevice, s));
-    if (total) {
+    const uint64_t lo = ch.lo, k = ch.hi - ch.lo;
+    const RowMsgLayout L = chunk_layout(ch);
+    if (prefix && k)
+        HIP_TRY(hipMemcpyAsync(d_nz[nxt] + lo * ntw, msg + L.nz, (size_t)k * ntw * 8, hipMemcpyDeviceToDevice, s));
+    if (r1 > r0 && k) {
         const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((k + 3) / 4, 4096));
         k_move_rows<false><<<g, 256, 0, s>>>(d_F[nxt], stride, lo, k, msg + L.nz, ntw,
                                              reinterpret_cast<const uint32_t*>(msg + L.off),
-                                             const_cast<uint64_t*>(msg + L.rows));
+                                             const_cast<uint64_t*>(rows), r0, r1, prefix ? msg : nullptr);
         HIP_TRY(hipGetLastError());
     }
-    if (wlive) {
-        k_or_words<<<(wlive + 255) / 256, 256, 0, s>>>(msg + L.live, wlive, d_live[lv]);
+    if (prefix && ch.wlive) {
+        k_or_words<<<(ch.wlive + 255) / 256, 256, 0, s>>>(msg + L.live, ch.wlive, d_live[lv]);
         HIP_TRY(hipGetLastError());
     }
-    exchange_bytes_in += words * 8;
     return GOSSIP_OK;
 }
 
@@ -3279,7 +3223,8 @@ int gossip_engine::rehearse_exchange(int64_t t) {
         if (hi <= lo) continue;
         hipEvent_t a = timing ? get_event() : nullptr, b = timing ? get_event() : nullptr;
         if (timing) HIP_TRY(hipEventRecord(a, stream));
-        int rc = pack_range(t, lo, hi, hw, stream);
+        const RowChunk ch{lo, hi, hw};
+        int rc = pack_msg(t, ch, MsgRoom::kExact, stream);
         if (rc) return rc;
         if (timing) {
             HIP_TRY(hipEventRecord(b, stream));
@@ -3289,7 +3234,11 @@ int gossip_engine::rehearse_exchange(int64_t t) {
         rr_bytes_max[r] = std::max<uint64_t>(rr_bytes_max[r], msg_words * 8);
         hipEvent_t c = timing ? get_event() : nullptr, d = timing ? get_event() : nullptr;
         if (timing) HIP_TRY(hipEventRecord(c, stream));
-        if ((rc = unpack_range(t, lo, hi, hw, d_msg, msg_words, stream))) return rc;
+        const RowMsgLayout L = chunk_layout(ch);
+        uint64_t nrows = 0;
+        L.nrows(msg_words, &nrows);  // (the message just packed: whole)
+        if ((rc = unpack_msg(t, ch, d_msg, d_msg + L.rows, 0, nrows, true, stream))) return rc;
+        exchange_bytes_in += msg_words * 8;
         if (timing) {
             HIP_TRY(hipEventRecord(d, stream));
             rr_events.push_back({r, 2u, c, d});
@@ -3312,64 +3261,6 @@ void gossip_engine::rehearse_harvest() {
     rr_events.clear();
 }
 
-// Pack rows [lo, hi) of F_next into d_msg in the device-sized layout (dev_layout; the header = the
-// row count, written on the device): no host wait.  d_msg holds the worst case, every tile row.
-int gossip_engine::pack_dev(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, hipStream_t s) {
-    const int nxt = fcur ^ 1, lv = (int)(t % 3);
-    const uint64_t k = hi - lo;
-    const DevLayout L = dev_layout(k, ntw, wlive);
-    int rc = ensure_dev(d_msg, msg_cap, L.rows + 16ull * k * (hw / kTileWords));
-    if (rc) return rc;
-    if (k + 1 > cnt_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        hipFree(d_cnt);
-        cnt_cap = k + 1;
-        HIP_TRY(hipMalloc(&d_cnt, cnt_cap * 4));
-    }
-    uint32_t* off = reinterpret_cast<uint32_t*>(d_msg + L.off);
-    k_pack_count<<<(uint32_t)((k + 1 + 255) / 256), 256, 0, s>>>(d_nz[nxt] + lo * ntw, k, ntw, d_msg + L.nz, d_cnt);
-    HIP_TRY(hipGetLastError());
-    size_t tmp = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_cnt, off, (int)(k + 1), s));
-    if (tmp > scan_tmp_bytes) {  // (first use of a chunk size only)
-        HIP_TRY(hipStreamSynchronize(s));
-        hipFree(d_scan_tmp);
-        scan_tmp_bytes = tmp;
-        HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
-    }
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, tmp, d_cnt, off, (int)(k + 1), s));
-    k_msg_header<<<1, 1, 0, s>>>(off + k, d_msg);
-    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((k + 3) / 4, 4096));
-    k_move_rows<true><<<g, 256, 0, s>>>(d_F[nxt], stride, lo, k, d_msg + L.nz, ntw, off, d_msg + L.rows);
-    HIP_TRY(hipGetLastError());
-    if (wlive) HIP_TRY(hipMemcpyAsync(d_msg + L.live, d_live[lv], (size_t)wlive * 8, hipMemcpyDeviceToDevice, s));
-    return GOSSIP_OK;
-}
-
-// Unpack message rows [r0, r1) of another rank's rows [lo, hi): `msg` is its prefix (header,
-// occupancy, offsets, liveness), `rows` points at message row r0.  prefix: first round -- also
-// the occupancy and liveness words, and r1 capped by the header's row count on the device.
-int gossip_engine::unpack_dev(int64_t t, uint64_t lo, uint64_t hi, uint32_t wlive, const uint64_t* msg,
-                              const uint64_t* rows, uint64_t r0, uint64_t r1, bool prefix, hipStream_t s) {
-    const int nxt = fcur ^ 1, lv = (int)(t % 3);
-    const uint64_t k = hi - lo;
-    const DevLayout L = dev_layout(k, ntw, wlive);
-    if (prefix && k)
-        HIP_TRY(hipMemcpyAsync(d_nz[nxt] + lo * ntw, msg + L.nz, (size_t)k * ntw * 8, hipMemcpyDeviceToDevice, s));
-    if (r1 > r0 && k) {
-        const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((k + 3) / 4, 4096));
-        k_move_rows<false><<<g, 256, 0, s>>>(d_F[nxt], stride, lo, k, msg + L.nz, ntw,
-                                             reinterpret_cast<const uint32_t*>(msg + L.off),
-                                             const_cast<uint64_t*>(rows), r0, r1, prefix ? msg : nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    if (prefix && wlive) {
-        k_or_words<<<(wlive + 255) / 256, 256, 0, s>>>(msg + L.live, wlive, d_live[lv]);
-        HIP_TRY(hipGetLastError());
-    }
-    return GOSSIP_OK;
-}
-
 // Row partition over RCCL, pipelined, with device-side sizes.  Per row chunk c, once the engine
 // stream has pulled it (ev_chunk[c]), the exchange stream packs the rank's rows (row count in the
 // message header, on the device), all-gathers the ranks' row counts into d_tot (device), and
@@ -3384,7 +3275,6 @@ int gossip_engine::exchange_rccl(int64_t t) {
     int rc = ensure_xstream();
     if (rc) return rc;
     const uint32_t R = row_count;
-    if (xcap.size() != (size_t)R * kMaxChunks) xcap.assign((size_t)R * kMaxChunks, 0ull);
     if (!d_tot) {
         HIP_TRY(hipMalloc(&d_tot, (size_t)R * kMaxChunks * 8));
         HIP_TRY(hipHostMalloc(&h_tot, (size_t)R * kMaxChunks * 8, hipHostMallocDefault));
@@ -3401,29 +3291,19 @@ int gossip_engine::exchange_rccl(int64_t t) {
             if (all[r] != nchunks) return set_error(GOSSIP_EINVAL, "row exchange: ranks use different xchunks options");
         xchunks_checked = true;
     }
-    auto geom = [&](uint32_t r, uint32_t c, uint64_t* lo, uint64_t* hi, uint32_t* wl) {
-        chunk_rows(r, c, lo, hi);
-        *wl = (c + 1 >= nchunks) ? hw : 0u;  // liveness rides in the last chunk
-    };
     // receive buffers for the whole tick: [c][r] prefix + capacity rows
     std::vector<uint64_t> at((size_t)nchunks * R, 0ull);
     uint64_t tot_words = 0;
     for (uint32_t c = 0; c < nchunks; c++)
         for (uint32_t r = 0; r < R; r++) {
             if (r == row_rank) continue;
-            uint64_t lo, hi;
-            uint32_t wl;
-            geom(r, c, &lo, &hi, &wl);
             at[(size_t)c * R + r] = tot_words;
-            tot_words += dev_layout(hi - lo, ntw, wl).rows + 16ull * xcap[(size_t)r * kMaxChunks + c];
+            tot_words += chunk_layout(chunk_rows(r, c)).total_words(xcap_at(r, c));
         }
     if ((rc = ensure_dev(d_recv_msgs, recv_cap, std::max<uint64_t>(tot_words, 1)))) return rc;
     for (uint32_t c = 0; c < nchunks; c++) {
-        uint64_t lo, hi;
-        uint32_t wl;
-        geom(row_rank, c, &lo, &hi, &wl);
         HIP_TRY(hipStreamWaitEvent(xstream, ev_chunk[c], 0));
-        if ((rc = pack_dev(t, lo, hi, wl, xstream))) return rc;
+        if ((rc = pack_msg(t, chunk_rows(row_rank, c), MsgRoom::kWorstCase, xstream))) return rc;
         COMM_TRY(ncclAllGather(d_msg, d_tot + (size_t)c * R, 1, ncclUint64, comm, xstream));
         {
             // ONE issue bracket around the whole group: `aborted` is tested once,
@@ -3434,10 +3314,7 @@ int gossip_engine::exchange_rccl(int64_t t) {
             if (aborted.load()) return set_error(GOSSIP_ESTATE, "RCCL: the row partition was aborted");
             ncclResult_t gr = ncclGroupStart();
             for (uint32_t r = 0; r < R && gr == ncclSuccess; r++) {
-                uint64_t rlo, rhi;
-                uint32_t rwl;
-                geom(r, c, &rlo, &rhi, &rwl);
-                const uint64_t words = dev_layout(rhi - rlo, ntw, rwl).rows + 16ull * xcap[(size_t)r * kMaxChunks + c];
+                const uint64_t words = chunk_layout(chunk_rows(r, c)).total_words(xcap_at(r, c));
                 uint64_t* buf = r == row_rank ? d_msg : d_recv_msgs + at[(size_t)c * R + r];
                 gr = ncclBroadcast(buf, buf, words, ncclUint64, (int)r, comm, xstream);
                 if (r == row_rank) exchange_bytes_out += words * 8;
@@ -3449,13 +3326,9 @@ int gossip_engine::exchange_rccl(int64_t t) {
         }
         for (uint32_t r = 0; r < R; r++) {
             if (r == row_rank) continue;
-            uint64_t rlo, rhi;
-            uint32_t rwl;
-            geom(r, c, &rlo, &rhi, &rwl);
+            const RowChunk ch = chunk_rows(r, c);
             const uint64_t* msg = d_recv_msgs + at[(size_t)c * R + r];
-            if ((rc = unpack_dev(t, rlo, rhi, rwl, msg, msg + dev_layout(rhi - rlo, ntw, rwl).rows, 0,
-                                 xcap[(size_t)r * kMaxChunks + c], true, xstream)))
-                return rc;
+            if ((rc = unpack_msg(t, ch, msg, msg + chunk_layout(ch).rows, 0, xcap_at(r, c), true, xstream))) return rc;
         }
     }
     // the tick's one host wait: every rank's row counts
@@ -3463,38 +3336,28 @@ int gossip_engine::exchange_rccl(int64_t t) {
     HIP_TRY(hipStreamSynchronize(xstream));
     for (uint32_t c = 0; c < nchunks; c++) {
         for (uint32_t r = 0; r < R; r++) {
-            uint64_t& cap = xcap[(size_t)r * kMaxChunks + c];
-            const uint64_t tot = h_tot[(size_t)c * R + r];
+            const uint64_t cap = xcap_at(r, c), tot = h_tot[(size_t)c * R + r];
             if (tot <= cap) continue;
             // second round (identical decision on every rank): rows [cap, tot) of rank r, chunk c
-            uint64_t rlo, rhi;
-            uint32_t rwl;
-            geom(r, c, &rlo, &rhi, &rwl);
-            const DevLayout L = dev_layout(rhi - rlo, ntw, rwl);
-            const uint64_t words = 16ull * (tot - cap);
+            const RowChunk ch = chunk_rows(r, c);
+            const uint64_t words = (uint64_t)kTileWords * (tot - cap);
             if (r == row_rank) {
-                if ((rc = pack_dev(t, rlo, rhi, rwl, xstream))) return rc;  // (d_msg held a later chunk)
-                COMM_TRY(ncclBroadcast(d_msg + L.rows + 16ull * cap, d_msg + L.rows + 16ull * cap, words, ncclUint64,
-                                       (int)r, comm, xstream));
+                if ((rc = pack_msg(t, ch, MsgRoom::kWorstCase, xstream))) return rc;  // (d_msg held a later chunk)
+                uint64_t* tail = d_msg + chunk_layout(ch).total_words(cap);
+                COMM_TRY(ncclBroadcast(tail, tail, words, ncclUint64, (int)r, comm, xstream));
                 exchange_bytes_out += words * 8;
             } else {
                 if ((rc = ensure_dev(d_ovf, ovf_cap, words))) return rc;
                 COMM_TRY(ncclBroadcast(d_ovf, d_ovf, words, ncclUint64, (int)r, comm, xstream));
                 exchange_bytes_in += words * 8;
-                if ((rc = unpack_dev(t, rlo, rhi, rwl, d_recv_msgs + at[(size_t)c * R + r], d_ovf, cap, tot, false,
-                                     xstream)))
+                if ((rc = unpack_msg(t, ch, d_recv_msgs + at[(size_t)c * R + r], d_ovf, cap, tot, false, xstream)))
                     return rc;
                 HIP_TRY(hipStreamSynchronize(xstream));  // (d_ovf is reused by the next overflow)
             }
-            x_overflow_rounds++;
         }
-        for (uint32_t r = 0; r < R; r++) {  // capacities: 1.25x the largest count seen (rows),
-            uint64_t& cap = xcap[(size_t)r * kMaxChunks + c];  // at most every tile row of the chunk
-            const uint64_t tot = h_tot[(size_t)c * R + r];
-            uint64_t rlo, rhi;
-            uint32_t rwl;
-            geom(r, c, &rlo, &rhi, &rwl);
-            if (tot > cap) cap = std::min<uint64_t>(tot + tot / 4 + 16, (rhi - rlo) * (hw / kTileWords));
+        for (uint32_t r = 0; r < R; r++) {  // the next tick's capacities
+            const RowChunk ch = chunk_rows(r, c);
+            xcap_at(r, c) = gossip::row_msg_next_cap(h_tot[(size_t)c * R + r], xcap_at(r, c), ch.hi - ch.lo, hw);
         }
     }
     return GOSSIP_OK;
@@ -4319,18 +4182,9 @@ int gossip_engine_group_run(gossip_engine** es, uint32_t count, int64_t tick_end
                 }
             }
             for (uint32_t c = 0; c < e0->nchunks && !e0->fused_rows; c++) {
-                auto geom = [&](uint32_t r, uint64_t* lo, uint64_t* hi, uint32_t* wl) {
-                    e0->chunk_rows(r, c, lo, hi);
-                    *wl = (c + 1 >= e0->nchunks) ? e0->hw : 0u;
-                };
                 for (uint32_t r = 0; r < count; r++) {
                     gossip_engine* e = es[r];
-                    if (e->xcap.size() != (size_t)count * gossip_engine::kMaxChunks)
-                        e->xcap.assign((size_t)count * gossip_engine::kMaxChunks, 0ull);
-                    uint64_t lo, hi;
-                    uint32_t wl;
-                    geom(r, &lo, &hi, &wl);
-                    int rc = e->pack_dev(t, lo, hi, wl, e->stream);
+                    int rc = e->pack_msg(t, e->chunk_rows(r, c), gossip_engine::MsgRoom::kWorstCase, e->stream);
                     if (rc) return rc;
                     HIP_TRY(hipStreamSynchronize(e->stream));
                 }
@@ -4341,38 +4195,29 @@ int gossip_engine_group_run(gossip_engine** es, uint32_t count, int64_t tick_end
                     gossip_engine* e = es[d];
                     for (uint32_t r = 0; r < count; r++) {
                         if (r == d) continue;
-                        uint64_t lo, hi;
-                        uint32_t wl;
-                        geom(r, &lo, &hi, &wl);
-                        const DevLayout L = dev_layout(hi - lo, e->ntw, wl);
-                        const uint64_t cap = e->xcap[(size_t)r * gossip_engine::kMaxChunks + c];
-                        int rc = e->ensure_dev(e->d_recv_msgs, e->recv_cap, L.rows + 16ull * cap);
+                        const RowChunk ch = e->chunk_rows(r, c);
+                        const RowMsgLayout L = e->chunk_layout(ch);
+                        const uint64_t cap = e->xcap_at(r, c);
+                        int rc = e->ensure_dev(e->d_recv_msgs, e->recv_cap, L.total_words(cap));
                         if (rc) return rc;
                         // first round: prefix + the first `cap` rows (the header caps the unpack)
-                        HIP_TRY(hipMemcpyAsync(e->d_recv_msgs, es[r]->d_msg, (L.rows + 16ull * cap) * 8,
+                        HIP_TRY(hipMemcpyAsync(e->d_recv_msgs, es[r]->d_msg, L.total_words(cap) * 8,
                                                hipMemcpyDeviceToDevice, e->stream));
-                        if ((rc = e->unpack_dev(t, lo, hi, wl, e->d_recv_msgs, e->d_recv_msgs + L.rows, 0, cap, true,
-                                                e->stream)))
+                        if ((rc = e->unpack_msg(t, ch, e->d_recv_msgs, e->d_recv_msgs + L.rows, 0, cap, true, e->stream)))
                             return rc;
                         if (tot[r] > cap) {  // second round: rows [cap, tot)
-                            const uint64_t words = 16ull * (tot[r] - cap);
+                            const uint64_t words = (uint64_t)kTileWords * (tot[r] - cap);
                             if ((rc = e->ensure_dev(e->d_ovf, e->ovf_cap, words))) return rc;
-                            HIP_TRY(hipMemcpyAsync(e->d_ovf, es[r]->d_msg + L.rows + 16ull * cap, words * 8,
+                            HIP_TRY(hipMemcpyAsync(e->d_ovf, es[r]->d_msg + L.total_words(cap), words * 8,
                                                    hipMemcpyDeviceToDevice, e->stream));
-                            if ((rc = e->unpack_dev(t, lo, hi, wl, e->d_recv_msgs, e->d_ovf, cap, tot[r], false,
-                                                    e->stream)))
+                            if ((rc = e->unpack_msg(t, ch, e->d_recv_msgs, e->d_ovf, cap, tot[r], false, e->stream)))
                                 return rc;
-                            e->x_overflow_rounds++;
                         }
                         HIP_TRY(hipStreamSynchronize(e->stream));  // (receive buffers are reused)
                     }
-                    for (uint32_t r = 0; r < count; r++) {  // (at most every tile row of the chunk)
-                        uint64_t& cap = e->xcap[(size_t)r * gossip_engine::kMaxChunks + c];
-                        uint64_t lo, hi;
-                        uint32_t wl;
-                        geom(r, &lo, &hi, &wl);
-                        if (tot[r] > cap)
-                            cap = std::min<uint64_t>(tot[r] + tot[r] / 4 + 16, (hi - lo) * (e->hw / kTileWords));
+                    for (uint32_t r = 0; r < count; r++) {  // the next tick's capacities
+                        const RowChunk ch = e->chunk_rows(r, c);
+                        e->xcap_at(r, c) = gossip::row_msg_next_cap(tot[r], e->xcap_at(r, c), ch.hi - ch.lo, e->hw);
                     }
                 }
             }
@@ -4580,7 +4425,9 @@ static int export_message(gossip_engine* e, uint32_t chunk, void* buf, uint64_t 
     if (e->packed_tick != e->cur || e->packed_chunk != chunk) {  // pack once per (tick, chunk)
         const uint32_t after = chunk == gossip_engine::kWholeRows ? e->nchunks - 1u : chunk;
         HIP_TRY(hipStreamWaitEvent(e->xstream, e->ev_chunk[after], 0));
-        if ((rc = e->pack_rows(e->cur, chunk, e->xstream))) return rc;
+        // (one host wait: the row count sizes the message)
+        if ((rc = e->pack_msg(e->cur, e->chunk_rows(e->row_rank, chunk), gossip_engine::MsgRoom::kExact, e->xstream)))
+            return rc;
         e->packed_tick = e->cur;
         e->packed_chunk = chunk;
     }
@@ -4600,6 +4447,12 @@ static int import_message(gossip_engine* e, uint32_t rank, uint32_t chunk, const
         return set_error(GOSSIP_EINVAL, "exchange_import: bad rank or buffer");
     if (chunk != gossip_engine::kWholeRows && chunk >= e->nchunks)
         return set_error(GOSSIP_EINVAL, "exchange_import_chunk: chunk >= gossip_engine_exchange_chunks");
+    const RowChunk ch = e->chunk_rows(rank, chunk);
+    const RowMsgLayout L = e->chunk_layout(ch);
+    uint64_t nrows = 0;  // (follows from the size: no header read-back)
+    if (!L.nrows(bytes / 8, &nrows))
+        return set_error(GOSSIP_EINVAL, "row exchange: message of rank " + std::to_string(rank) +
+                                            " has the wrong size (ranks diverged?)");
     HIP_TRY(hipSetDevice(e->device));
     if ((rc = e->ensure_dev(e->d_recv_msgs, e->recv_cap, std::max<uint64_t>(bytes / 8, 1)))) return rc;
     // The unpack ORs liveness into d_live and writes F_next / nz_next rows that this tick's
@@ -4610,7 +4463,8 @@ static int import_message(gossip_engine* e, uint32_t rank, uint32_t chunk, const
         HIP_TRY(hipStreamWaitEvent(e->xstream, e->ev_chunk[after], 0));
     }
     HIP_TRY(hipMemcpyAsync(e->d_recv_msgs, buf, bytes, hipMemcpyHostToDevice, e->xstream));
-    if ((rc = e->unpack_rows(e->cur, rank, chunk, e->d_recv_msgs, bytes / 8, e->xstream))) return rc;
+    if ((rc = e->unpack_msg(e->cur, ch, e->d_recv_msgs, e->d_recv_msgs + L.rows, 0, nrows, true, e->xstream))) return rc;
+    e->exchange_bytes_in += bytes;
     HIP_TRY(hipStreamSynchronize(e->xstream));  // (the receive buffer is reused by the next import)
     return GOSSIP_OK;
 }

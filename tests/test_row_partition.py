@@ -3,7 +3,9 @@ rows and the ranks exchange frontier rows, tile occupancy and liveness after eve
 `xchunks` row chunks (the pipelined exchange).  The lockstep one-device backend
 (gossip_engine_group_run) must give per-node counters that sum to the single engine's and to
 ORACLE A's bit for bit; the RCCL backend is exercised on one rank (ncclBroadcast / all-gather
-over a 1-rank communicator)."""
+over a 1-rank communicator); the host-staged calls, with both ranks in this process, must give
+each rank the counters it has on the lockstep backend, account for every exported byte and refuse
+a message of the wrong size."""
 import numpy as np
 import pytest
 
@@ -167,6 +169,119 @@ def test_xchunks_mismatch_is_refused(gossip):
         gossip.group_run(ranks)
     with pytest.raises(gossip.GossipError, match="xchunks"):
         ranks[0].set_option("xchunks", 17)
+    for e in ranks:
+        e.close()
+
+
+STATS = SUM + ("peers", "sockets")
+# host-staged stepping in one process: n = 1100 in 512-row blocks gives ranks of 1024 and 76 rows; at
+# xchunks = 2 rank 0's chunks are one granule each and rank 1's last chunk is EMPTY but carries its
+# liveness words -- the smallest case with a non-empty chunk, an empty one and liveness in an
+# empty last chunk
+STAGED = dict(n=1100, p=0.02, R=2, seed=31, t_cut_s=6.6, xchunks=2)
+
+
+def _staged_ranks(gossip, inputs):
+    topo, t_cut, ev = inputs
+    ranks = [_engine(gossip, STAGED["n"], t_cut, topo, ev, gossip.MODE_CSR, 0, part=(r, STAGED["R"]))
+             for r in range(STAGED["R"])]
+    for e in ranks:
+        e.set_option("xchunks", STAGED["xchunks"])
+    return ranks
+
+
+def _swap(ranks, chunk, sizes):
+    # one exchange step: every rank exports (chunk None = its whole rows), every other rank imports
+    msgs = [e.exchange_export() if chunk is None else e.exchange_export_chunk(chunk) for e in ranks]
+    for d, e in enumerate(ranks):
+        for r, m in enumerate(msgs):
+            if r == d:
+                sizes[r].append(m.nbytes)
+            elif chunk is None:
+                e.exchange_import(r, m)
+            else:
+                e.exchange_import_chunk(r, chunk, m)
+    return msgs
+
+
+@pytest.fixture(scope="module")
+def staged(gossip):
+    """One workload on the single engine, on the lockstep backend and host-staged (chunk calls, then
+    whole-rows calls) with both ranks in this process.  Computed once; the tests only read it."""
+    inputs = _inputs(gossip, STAGED["n"], STAGED["p"], STAGED["seed"], STAGED["t_cut_s"])
+    topo, t_cut, ev = inputs
+    ref = _engine(gossip, STAGED["n"], t_cut, topo, ev, gossip.MODE_CSR, 0)
+    ref.run()
+    ref.sync()
+    out = {"single": ref.stats()}
+    ref.close()
+    ranks = _staged_ranks(gossip, inputs)
+    gossip.group_run(ranks)
+    for e in ranks:
+        e.sync()
+    out["lockstep"] = [e.stats() for e in ranks]
+    for e in ranks:
+        e.close()
+    for how in ("chunked", "whole"):
+        ranks = _staged_ranks(gossip, inputs)
+        sizes = [[] for _ in ranks]  # per rank: bytes of every message it exported, in order
+        ticks = 0
+        while True:
+            more = [e.tick_begin() for e in ranks]
+            assert all(more) or not any(more)
+            if not more[0]:
+                break
+            for c in (range(STAGED["xchunks"]) if how == "chunked" else (None,)):
+                _swap(ranks, c, sizes)
+            for e in ranks:
+                e.tick_end()
+            ticks += 1
+        for e in ranks:
+            e.sync()
+        cs = [e.counters() for e in ranks]
+        out[how] = dict(stats=[e.stats() for e in ranks], sizes=sizes, ticks=ticks,
+                        sent=[int(c.exchange_bytes_sent) for c in cs],
+                        received=[int(c.exchange_bytes_received) for c in cs])
+        for e in ranks:
+            e.close()
+        print(f"host-staged {how}: {ticks} ticks, exported bytes per rank {[sum(s) for s in sizes]}, "
+              f"messages per rank {[len(s) for s in sizes]}, largest {[max(s) for s in sizes]}")
+    return out
+
+
+@pytest.mark.parametrize("how", ["chunked", "whole"])
+def test_host_staged_equals_lockstep_per_rank(staged, how):
+    got = staged[how]["stats"]
+    assert staged[how]["ticks"] > 100
+    for r, (g, w) in enumerate(zip(got, staged["lockstep"])):
+        for k in STATS:
+            assert np.array_equal(getattr(g, k), getattr(w, k)), (r, k)
+    for k in SUM:
+        total = sum(getattr(g, k).astype(np.uint64) for g in got)
+        assert np.array_equal(total, getattr(staged["single"], k).astype(np.uint64)), k
+    assert sum(int(g.recv.sum()) for g in got) > 0
+
+
+@pytest.mark.parametrize("how", ["chunked", "whole"])
+def test_host_staged_byte_accounting(staged, how):
+    run = staged[how]
+    per_tick = STAGED["xchunks"] if how == "chunked" else 1
+    for r in range(STAGED["R"]):
+        assert len(run["sizes"][r]) == run["ticks"] * per_tick
+        assert all(b % 8 == 0 and b > 0 for b in run["sizes"][r])
+        assert sum(run["sizes"][r]) == run["sent"][r]
+        assert run["received"][r] == run["sent"][1 - r]
+
+
+def test_host_staged_import_checks_the_size(gossip):
+    ranks = _staged_ranks(gossip, _inputs(gossip, STAGED["n"], STAGED["p"], STAGED["seed"], STAGED["t_cut_s"]))
+    for e in ranks:
+        assert e.tick_begin()
+    msgs = _swap(ranks, 0, [[] for _ in ranks])  # (the whole messages are accepted)
+    assert msgs[0].size > 8
+    with pytest.raises(gossip.GossipError, match="wrong size") as ex:
+        ranks[1].exchange_import_chunk(0, 0, msgs[0][:-8])
+    assert ex.value.code == gossip.E_INVAL
     for e in ranks:
         e.close()
 
