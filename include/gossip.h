@@ -328,8 +328,87 @@ typedef struct gossip_fanout_counters {
     uint64_t bytes;         /* bytes they had to move (model: 9 B + 2 bits per entry, 68 B per
                                node, 8 B per kept entry)                                          */
 } gossip_fanout_counters;
-/* Since the last gossip_engine_reset_timing; zeros on an engine without fanout. */
+/* Since the last gossip_engine_reset_timing; zeros on an engine without fanout and without faults.
+ * On a faults-only engine (gossip_engine_set_outages / _set_link_loss and no fanout setter) these are
+ * the thinning passes of the fault mode: every threshold is 0xffffffff there. */
 int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* c);
+
+/* Fault injection: node outages and message loss, applied on the GPU in the per-tick thinning pass of
+ * fanout mode (k_fanout_count_faults, csrc/fanout_kernel.h).  Time is in ticks as in fanout mode: a
+ * share generated at g is sent in tick floor(g / L); a first arrival at hop h happens in tick
+ * floor(g / L) + h and forwards in that same tick; Sends made in tick T are pulled in tick T + 1.
+ *   OUTAGES.  Each node has a set of half-open tick intervals [tick_from, tick_to), in absolute ticks as
+ * gossip_engine_first_tick counts them; the node is DOWN in every tick of them.
+ *   - A generation event whose tick floor(ns / L) is a down tick of its node does not happen: it is not
+ *     counted in gen, gets no column, its reach row is all zero and it is not in the snapshot generation
+ *     totals -- the treatment of a generation at a node without peers, applied at the same place
+ *     (gossip_engine_set_schedule, on the host).
+ *   - A Send u -> v made in tick T is delivered only if v is up in tick T + 1.  The Send is still made:
+ *     it is counted in sent[u] and edge_events (the sender does not know).  It delivers nothing: no recv,
+ *     no trace record, no reach count.
+ *   - There is no sender test: a node forwards in the tick in which it first received, so a sender is up.
+ *   - A node that comes back up keeps its seen set.  It has missed what arrived while it was down and
+ *     gets such a share later only if some peer first-receives it later: crash-recover without state loss
+ *     and without retransmission.
+ *   MESSAGE LOSS.  A Send u -> v, copy c, made in tick T is lost iff
+ *     lo = min(u, v), hi = max(u, v)
+ *     y  = Philox4x32-10(counter = (lo, hi, (uint32)T, c),
+ *                        key = (seed & 0xffffffff, (seed >> 32) ^ 0x4C4F5353))
+ *     w  = (u < v) ? y[0] : y[1]
+ *     lost = (loss_thr == 0xffffffff) || (w < loss_thr)
+ * loss_thr is one threshold for the whole graph, floor(p * 2^32): 0 never, 0xffffffff always.  A lost
+ * Send is made and counted in sent, like a Send to a down node, and delivers nothing.  The draw belongs
+ * to (sender, receiver, copy, tick), not to a share (the round-based model of fanout mode).  Loss has its
+ * own key constant and its own seed: the loss draw of a link does not change when fanout is switched on
+ * or its seed changes.
+ *   WITH FANOUT.  Fanout decides whether a Send is made (an unselected Send is not counted, as before);
+ * faults decide whether a made Send arrives.  A peer-list entry (row v, peer u) survives tick T's
+ * thinning iff v is up in T + 1 and some copy c < mult(u -> v) is selected and not lost.  The result is a
+ * pure function of (graph, events, latency, cut, thresholds, fanout seed, outages, loss_thr, loss seed):
+ * no tuning option, tile layout or share sharding changes it.
+ *   gossip_engine_set_outages: after the graph and before the schedule (GOSSIP_ESTATE otherwise).  A
+ * second call replaces the first; count 0 clears the outages.  GOSSIP_EINVAL, naming the index, for
+ * node >= n or tick_from >= tick_to.  Overlapping or touching intervals of one node are merged.  A
+ * tick_to beyond 32 bits means "for the rest of the run" (ticks fit 32 bits in this mode).
+ *   gossip_engine_set_link_loss: the same place in the call order; loss_thr 0 switches loss off again.
+ *   Either setter on an engine without fanout turns the thinning path on with every threshold
+ * 0xffffffff: a flood whose lists are thinned by faults only.  What fanout mode refuses is refused here
+ * with the same messages (GOSSIP_F_HOP_BATCH, link timing, GOSSIP_F_HANDSHAKE, a row partition,
+ * GOSSIP_MODE_DENSE -- AUTO resolves to CSR --, ticks beyond 32 bits, forcing young, pull_push,
+ * young_skip or young_idle on), and share ids must be unique.  The fault setters and the fanout setters
+ * may be called in either order; none discards what another set.
+ *   gossip_fault_lost: the loss rule itself, 1 / 0; needs no engine and no device. */
+typedef struct gossip_outage {
+    uint32_t node;
+    uint32_t pad;
+    int64_t tick_from; /* down in [tick_from, tick_to) */
+    int64_t tick_to;
+} gossip_outage;
+int gossip_engine_set_outages(gossip_engine* e, uint64_t count, const gossip_outage* outages);
+int gossip_engine_set_link_loss(gossip_engine* e, uint32_t loss_thr, uint64_t seed);
+int gossip_fault_lost(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy, int64_t tick,
+                      uint32_t loss_thr);
+typedef struct gossip_fault_counters {
+    uint64_t launches;            /* ticks thinned with faults (the count pass with faults ran)         */
+    uint64_t down_node_ticks;     /* nodes down in the tick the thinning serves (T + 1), summed over
+                                     those ticks                                                        */
+    uint64_t lost_copies;         /* in-side copies that fanout selected at an up receiver and the loss
+                                     draw dropped, summed over ticks                                    */
+    uint64_t down_copies;         /* in-side copies that fanout selected into a down row, summed over
+                                     ticks                                                              */
+    uint64_t dropped_generations; /* generation events dropped in a down tick of their node (since
+                                     creation: counted by gossip_engine_set_schedule)                   */
+} gossip_fault_counters;
+/* Reads an outage file for gossip_engine_set_outages (gossip_sim --outages): lines "node from_ns
+ * to_ns", unsigned decimal fields, parsed as strictly as gossip_topology_load_links parses link files (a
+ * malformed line fails with GOSSIP_EINVAL naming the line).  A node is down in tick T iff
+ * from_ns <= T * latency_ns < to_ns: tick_from = ceil(from_ns / L), tick_to = ceil(to_ns / L).  Lines
+ * that give an empty tick range are skipped and counted in *skipped.  *count = the outages read; at most
+ * cap of them are written to out (out = NULL, cap = 0 sizes). */
+int gossip_outages_load(uint32_t num_nodes, int64_t latency_ns, const char* path, uint64_t cap,
+                        gossip_outage* out, uint64_t* count, uint64_t* skipped);
+/* The first four since the last gossip_engine_reset_timing; all zero on an engine without faults. */
+int gossip_engine_get_fault_counters(gossip_engine* e, gossip_fault_counters* c);
 /* Tuning options of one engine (results never depend on them; A/B runs and tests).  The
  * environment variable in brackets gives the default:
  *   "pull_nt"          -1 auto (non-temporal rows when the live frontier n x wact x 8 B exceeds
@@ -555,7 +634,8 @@ int gossip_engine_reset_timing(gossip_engine* e);
  *             other frontier buffer, 8 folded rows masked with seen rows; 1 k_reach_slots with every
  *             counter in LDS, 2 k_reach_slots with more than 8 write-sparse tiles (the 8 oldest
  *             tiles' counters in LDS, a global atomic per entry of the others); GOSSIP_K_FANOUT: 1 the
- *             count pass, 2 the compact pass (strided: a wave looped over several 64-node chunks);
+ *             count pass, 2 the compact pass, 3 the count pass with faults (k_fanout_count_faults, in place
+ *             of 1 on an engine with outages or loss; strided: a wave looped over several 64-node chunks);
  *             0 otherwise
  *   launches  launches of that variant
  *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's

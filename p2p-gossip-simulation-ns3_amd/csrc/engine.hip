@@ -1053,6 +1053,21 @@ struct gossip_engine {
     int fanout_setup(const uint32_t* thr, uint64_t seed);
     void fanout_free();                // every buffer above (a setter call that failed half-way, the destructor)
     bool fanout_allocated = false;     // the setter's allocations all succeeded
+    // ---- fault injection (gossip_engine_set_outages / _set_link_loss): a second reason to drop an entry
+    // in the thinning pass above, which either setter turns on (fanout = true, every threshold 0xffffffff,
+    // when no fanout setter ran).  Ticks with outages or loss run k_fanout_count_faults in place of
+    // k_fanout_count; a generation in a down tick of its node is dropped in set_schedule.
+    std::vector<uint32_t> h_out_off, h_out_from, h_out_to;  // merged intervals per node: offsets n + 1, ticks
+    uint32_t *d_out_off = nullptr, *d_out_from = nullptr, *d_out_to = nullptr;
+    uint64_t outage_bytes = 0;         // device bytes of the three (in device_bytes)
+    uint32_t loss_thr = 0;
+    uint64_t loss_seed = 0;
+    uint64_t fault_launches = 0, dropped_generations = 0;
+    bool faults() const { return !h_out_from.empty() || loss_thr != 0; }
+    bool down(uint32_t v, int64_t t) const {
+        return !h_out_from.empty() && t >= 0 && gossip::outage_down(h_out_off.data(), h_out_from.data(), h_out_to.data(), v, (uint64_t)t);
+    }
+    int outages_setup(uint64_t count, const gossip_outage* o);
 
     ~gossip_engine();
     int alloc_device();
@@ -1196,6 +1211,7 @@ gossip_engine::~gossip_engine() {
         hipEventDestroy(p.second);
     }
     fanout_free();
+    hipFree(d_out_off); hipFree(d_out_from); hipFree(d_out_to);
     if (comm && !aborted.load()) ncclCommDestroy(comm);  // (an aborted communicator is already freed)
     for (int k = 0; k < kRing; k++) {
         hipFree(d_ctl[k]); hipFree(d_births[k]); hipFree(d_gphase[k]); hipFree(d_wflags[k]);
@@ -1662,7 +1678,7 @@ int gossip_engine::alloc_device() {
     }
     device_bytes = 2 * bm + bm_seen + (d_sat ? 24ull : 16ull) * n * ntw + (uint64_t)n * 20 + nnz * 4 + ((uint64_t)n + 1) * 8 + 2ull * stride * 8 + slot_bytes +
                    kRing * ((uint64_t)stride * sizeof(WordCtl) + (uint64_t)bcap * sizeof(Birth) + pcap * 4);
-    device_bytes += fanout_bytes;  // (allocated by the fanout setter; 0 without one)
+    device_bytes += fanout_bytes + outage_bytes;  // (allocated by the fanout / fault setters; 0 without one)
     if (dense) {
         const uint64_t ft = (uint64_t)stride * 8 * n_pad;
         snz_nstw = (n_pad / kStageK + 63u) / 64u;
@@ -3712,6 +3728,54 @@ int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed) {
     return GOSSIP_OK;
 }
 
+// Node outages (gossip_engine_set_outages): the intervals clamped to 32-bit ticks, sorted, merged per
+// node (overlapping or touching) into a per-node CSR, on the host (set_schedule's drop) and on the device
+// (k_fanout_count_faults).  count 0 leaves n + 1 zero offsets: no node is ever down.
+int gossip_engine::outages_setup(uint64_t count, const gossip_outage* o) {
+    HIP_TRY(hipSetDevice(device));
+    struct Iv { uint32_t node, from, to; };
+    std::vector<Iv> iv;
+    iv.reserve(count);
+    for (uint64_t k = 0; k < count; k++) {  // (validated by the setter)
+        // (ticks fit 32 bits in this mode: a tick_to beyond them means "for the rest of the run")
+        const int64_t from = std::max<int64_t>(o[k].tick_from, 0), to = std::min<int64_t>(o[k].tick_to, 0xffffffffll);
+        if (from < to) iv.push_back({o[k].node, (uint32_t)from, (uint32_t)to});
+    }
+    std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& b) { return a.node != b.node ? a.node < b.node : a.from < b.from; });
+    std::vector<uint32_t> off((size_t)n + 1, 0u), from, to;
+    for (const Iv& x : iv) {
+        if (off[x.node + 1] && x.from <= to.back()) {  // (off[node + 1]: the node's intervals so far)
+            to.back() = std::max(to.back(), x.to);
+        } else {
+            from.push_back(x.from);
+            to.push_back(x.to);
+            off[x.node + 1]++;
+        }
+    }
+    for (uint32_t v = 0; v < n; v++) off[v + 1] += off[v];
+    const size_t m = from.size(), bytes = ((size_t)n + 1) * 4 + 2 * std::max<size_t>(m, 1) * 4;
+    uint32_t *d_off = nullptr, *d_from = nullptr, *d_to = nullptr;
+    if (hipMalloc(&d_off, ((size_t)n + 1) * 4) != hipSuccess || hipMalloc(&d_from, std::max<size_t>(m, 1) * 4) != hipSuccess ||
+        hipMalloc(&d_to, std::max<size_t>(m, 1) * 4) != hipSuccess) {
+        hipFree(d_off); hipFree(d_from); hipFree(d_to);
+        (void)hipGetLastError();
+        return set_error(GOSSIP_ENOMEM, "outages: device allocation failed");
+    }
+    hipError_t err = hipMemcpy(d_off, off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess && m) err = hipMemcpy(d_from, from.data(), m * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess && m) err = hipMemcpy(d_to, to.data(), m * 4, hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        hipFree(d_off); hipFree(d_from); hipFree(d_to);
+        HIP_TRY(err);
+    }
+    hipFree(d_out_off); hipFree(d_out_from); hipFree(d_out_to);  // a second call replaces the first
+    d_out_off = d_off; d_out_from = d_from; d_out_to = d_to;
+    device_bytes += bytes - outage_bytes;
+    outage_bytes = bytes;
+    h_out_off.swap(off); h_out_from.swap(from); h_out_to.swap(to);
+    return GOSSIP_OK;
+}
+
 // End of tick t: count pass (selection bitmap, per-node in-counts, sent), scan, compact pass -- all
 // on the engine stream, no host round trip.  The pull of t + 1 is launched after these.
 int gossip_engine::fanout_launch(int64_t t) {
@@ -3731,9 +3795,19 @@ int gossip_engine::fanout_launch(int64_t t) {
         HIP_TRY(hipEventRecord(e0, stream));
     }
     HIP_TRY(hipMemsetAsync(d_fbitmap, 0, ((size_t)(nnz + 63) / 64 + 1) * 8, stream));
-    gossip::k_fanout_count<<<grid, 256, 0, stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    ledger.add(gossip::LK_FANOUT, 1u, strided);
+    if (faults()) {  // outages or loss: the count pass that also drops down rows and lost copies
+        gossip::FaultArgs f;
+        f.out_off = d_out_off; f.out_from = d_out_from; f.out_to = d_out_to;
+        f.loss_seed = loss_seed; f.loss_thr = loss_thr;
+        gossip::k_fanout_count_faults<<<grid, 256, 0, stream>>>(a, f);
+        HIP_TRY(hipGetLastError());
+        ledger.add(gossip::LK_FANOUT, 3u, strided);
+        fault_launches++;
+    } else {
+        gossip::k_fanout_count<<<grid, 256, 0, stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        ledger.add(gossip::LK_FANOUT, 1u, strided);
+    }
     size_t tmp = fscan_tmp_bytes;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_fscan_tmp, tmp, FanoutCountIt(d_fcnt, FanoutCountCast()), d_rowptr_t, (int)(n + 1),
                                              stream));
@@ -4576,6 +4650,74 @@ int gossip_fanout_selected(uint64_t seed, uint32_t sender, uint32_t receiver, ui
     return gossip::fanout_selected(seed, sender, receiver, copy, (uint32_t)tick, thr) ? 1 : 0;
 }
 
+// ---- fault injection: both setters turn the thinning path on (a flood thinned by faults only: every
+// threshold 0xffffffff) unless a fanout setter already did, and keep what the other setters set
+static int thinning_on(gossip_engine* e) {
+    if (e->fanout) return GOSSIP_OK;
+    try {
+        std::vector<uint32_t> thr(e->n, gossip::kFanoutAlways);
+        return fanout_set(e, thr.data(), 0);
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+}
+
+int gossip_engine_set_outages(gossip_engine* e, uint64_t count, const gossip_outage* outages) {
+    if (e && count && !outages) return set_error(GOSSIP_EINVAL, "NULL argument");
+    if (int rc = fanout_check(e)) return rc;
+    for (uint64_t k = 0; k < count; k++) {  // (before anything changes: a refused call leaves the engine as it was)
+        const gossip_outage& o = outages[k];
+        if (o.node >= e->n)
+            return set_error(GOSSIP_EINVAL, "outage " + std::to_string(k) + ": node " + std::to_string(o.node) + " out of range");
+        if (o.tick_from >= o.tick_to)
+            return set_error(GOSSIP_EINVAL, "outage " + std::to_string(k) + ": tick_from " + std::to_string(o.tick_from) +
+                                                " >= tick_to " + std::to_string(o.tick_to) + " (an empty interval)");
+    }
+    if (int rc = thinning_on(e)) return rc;
+    try {
+        return e->outages_setup(count, outages);
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+}
+
+int gossip_engine_set_link_loss(gossip_engine* e, uint32_t loss_thr, uint64_t seed) {
+    if (int rc = fanout_check(e)) return rc;
+    if (int rc = thinning_on(e)) return rc;
+    if (!e->d_out_off) {  // (the count pass reads every node's offsets: no outages = n + 1 zeros)
+        try {
+            if (int rc = e->outages_setup(0, nullptr)) return rc;
+        } catch (const std::bad_alloc&) {
+            return set_error(GOSSIP_ENOMEM, "host allocation failed");
+        }
+    }
+    e->loss_thr = loss_thr;
+    e->loss_seed = seed;
+    return GOSSIP_OK;
+}
+
+int gossip_fault_lost(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy, int64_t tick, uint32_t loss_thr) {
+    return gossip::fault_lost(seed, sender, receiver, copy, (uint32_t)tick, loss_thr) ? 1 : 0;
+}
+
+int gossip_engine_get_fault_counters(gossip_engine* e, gossip_fault_counters* c) {
+    if (!e || !c) return set_error(GOSSIP_EINVAL, "NULL argument");
+    std::memset(c, 0, sizeof(*c));
+    c->dropped_generations = e->dropped_generations;
+    if (!e->fanout) return GOSSIP_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    std::vector<unsigned long long> st((size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas);
+    HIP_TRY(hipMemcpy(st.data(), e->d_fstat, st.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < gossip::kFanoutStatReplicas; r++) {
+        c->lost_copies += st[(size_t)r * gossip::kFanoutStatLine + 2];
+        c->down_copies += st[(size_t)r * gossip::kFanoutStatLine + 3];
+        c->down_node_ticks += st[(size_t)r * gossip::kFanoutStatLine + 4];
+    }
+    c->launches = e->fault_launches;
+    return GOSSIP_OK;
+}
+
 int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* c) {
     if (!e || !c) return set_error(GOSSIP_EINVAL, "NULL argument");
     std::memset(c, 0, sizeof(*c));
@@ -4637,13 +4779,18 @@ int gossip_engine_set_schedule(gossip_engine* e, uint64_t num_events, const goss
         {
             const int64_t t_reg = e->t0 + 3 * e->L;
             size_t o = 0;
+            uint64_t dropped = 0;
             for (size_t k = 0; k < e->ev.size(); k++) {
                 const gossip_gen_event& x = e->ev[k];
                 const bool no_peers = e->h_peers[x.node] == 0 ||
                                       (e->handshake && x.ns < t_reg && e->h_degc[x.node] == 0);
-                if (!no_peers) e->ev[o++] = x;
+                // fault injection: a generation in a down tick of its node does not happen (the same treatment)
+                const bool is_down = e->down(x.node, x.ns / e->L);
+                dropped += is_down;
+                if (!no_peers && !is_down) e->ev[o++] = x;
             }
             e->ev.resize(o);
+            e->dropped_generations = dropped;
         }
         if (e->handshake) {
             // A share sent before t_start + 2L is lost with its REGISTER segment and floods
@@ -5116,6 +5263,7 @@ int gossip_engine_reset_timing(gossip_engine* e) {
     e->timers_fanout.clear();
     e->fanout_ms_done = 0.0;
     e->fanout_launches = 0;
+    e->fault_launches = 0;
     if (e->d_fstat)
         HIP_TRY(hipMemsetAsync(e->d_fstat, 0, (size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas * 8, e->stream));
     if (e->d_rbytes) HIP_TRY(hipMemsetAsync(e->d_rbytes, 0, 8, e->stream));

@@ -24,6 +24,16 @@
 //                     -- rows are contiguous and in order, so the compaction is stable and needs no
 //                     per-entry row lookup.
 // Tick T + 1's k_pull launches read (rowptr_t, col_t) where they read (rowptr, col) in a flood.
+//
+// Fault injection (gossip.h, gossip_engine_set_outages / _set_link_loss) is a second reason to drop an
+// entry in the same pass: k_fanout_count_faults is the count pass with three additions.  Entry (row v,
+// peer u) survives iff v is up in tick T + 1 and some copy c < mult(u -> v) has fanout_pass && !lost,
+//     y = Philox4x32-10(counter = (lo, hi, (uint32)T, c), key = (seed & 0xffffffff, (seed >> 32) ^ "LOSS"))
+//     lost = loss_thr == 0xffffffff || (u < v ? y[0] : y[1]) < loss_thr        (u the sender)
+// with a seed of its own.  "v is down in T + 1" is a search of v's merged outage intervals (a per-node
+// CSR, outage_down below), decided once per node in the chunk prologue and kept in LDS next to s_thr; no
+// state is carried from tick to tick.  The out side is unchanged: a Send to a down node or a lost Send is
+// made and counted.  k_fanout_count stays the code it was (one body, two instantiations).
 #pragma once
 
 #include <stdint.h>
@@ -55,9 +65,40 @@ GOSSIP_HD uint32_t fanout_threshold(uint32_t k, uint32_t deg) {
     return deg <= k ? kFanoutAlways : (uint32_t)(((uint64_t)k << 32) / deg);
 }
 
+
+constexpr uint32_t kLossKey1 = 0x4C4F5353u;  // "LOSS": xor of the second key word of the loss draw
+
+// y[0], y[1] of the link {a, b} (either order), copy c, tick T
+GOSSIP_HD void loss_draw(uint64_t seed, uint32_t a, uint32_t b, uint32_t c, uint32_t tick, uint32_t y[2]) {
+    uint32_t ctr[4] = {a < b ? a : b, a < b ? b : a, tick, c};
+    philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32) ^ kLossKey1);
+    y[0] = ctr[0];
+    y[1] = ctr[1];
+}
+GOSSIP_HD bool loss_pass(uint32_t w, uint32_t thr) { return thr == 0xffffffffu || w < thr; }
+// THE definition of the loss rule: is the Send u -> v, copy c, made in tick T lost?
+GOSSIP_HD bool fault_lost(uint64_t seed, uint32_t u, uint32_t v, uint32_t c, uint32_t tick, uint32_t thr) {
+    uint32_t y[2];
+    loss_draw(seed, u, v, c, tick, y);
+    return loss_pass(u < v ? y[0] : y[1], thr);
+}
+// THE definition of "node v is down in tick t": its merged, ascending, disjoint intervals are
+// [from[k], to[k]) for k in [off[v], off[v + 1]); the last one that starts at or before t decides
+GOSSIP_HD bool outage_down(const uint32_t* off, const uint32_t* from, const uint32_t* to, uint32_t v, uint64_t t) {
+    const uint32_t first = off[v];
+    uint32_t lo = first, hi = off[v + 1];
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (from[mid] <= t) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo > first && t < to[lo - 1u];
+}
+
 #if defined(__HIPCC__)
 
-constexpr uint32_t kFanoutStatLine = 16, kFanoutStatReplicas = 64;  // 128-B lines of [selected_in, selected_out]
+// 128-B lines of [selected_in, selected_out, lost_copies, down_copies, down_node_ticks] (the last three: faults)
+constexpr uint32_t kFanoutStatLine = 16, kFanoutStatReplicas = 64;
 
 struct FanoutArgs {
     const int64_t* rowptr;   // the full graph
@@ -80,12 +121,44 @@ struct FanoutArgs {
     uint32_t n;
 };
 
-__global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) {
+// The two draws of the count pass with faults: fanout_draw (key1 = kFanoutKey1) and loss_draw (kLossKey1)
+// with their round keys formed round by round.  Left to itself the compiler hoists the 20 round keys of
+// each draw into SGPRs for the whole kernel; the 40, with the multipliers and the arguments, do not fit
+// the 102 and spill into VGPR lanes.  The empty asm makes each round's keys a value it cannot precompute:
+// two scalar adds per round, no spill.
+__device__ __forceinline__ void draw_rolling(uint64_t seed, uint32_t key1, uint32_t a, uint32_t b, uint32_t c, uint32_t tick,
+                                             uint32_t y[2]) {
+    uint32_t x[4] = {a < b ? a : b, a < b ? b : a, tick, c};
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ key1;
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        asm volatile("" : "+s"(k0), "+s"(k1));
+        philox4x32_round(x, k0, k1);
+        k0 += kPhiloxW0;
+        k1 += kPhiloxW1;
+    }
+    y[0] = x[0];
+    y[1] = x[1];
+}
+
+struct FaultArgs {
+    const uint32_t* out_off;   // n + 1: node v's outage intervals are [out_off[v], out_off[v + 1])
+    const uint32_t* out_from;  // ticks, merged and ascending per node
+    const uint32_t* out_to;
+    uint64_t loss_seed;
+    uint32_t loss_thr;         // 0: no loss, and no loss draw
+};
+
+template <bool FAULTS>
+__device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const FaultArgs f) {
     __shared__ uint32_t s_off[4][65], s_thr[4][64], s_in[4][64], s_out[4][64];
+    __shared__ uint32_t s_down[FAULTS ? 4 : 1][FAULTS ? 64 : 1];  // (faults) the row is down in tick + 1
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t nch = ((uint64_t)a.n + 63u) / 64u;
     unsigned long long tin = 0ull, tout = 0ull;
+    uint32_t tlost = 0u, tdownc = 0u, tdown = 0u;  // (faults) this lane's lost copies, copies into down rows, down nodes
+    const bool loss_on = FAULTS && f.loss_thr != 0u;  // uniform: a scalar branch
     for (uint64_t ch = (uint64_t)blockIdx.x * 4u + wv; ch < nch; ch += (uint64_t)gridDim.x * 4u) {
         const uint64_t c0 = ch * 64u, v = c0 + lane;
         const int64_t rp0 = a.rowptr[c0];
@@ -93,6 +166,11 @@ __global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) {
         s_off[wv][lane] = (uint32_t)(a.rowptr[v < a.n ? v : a.n] - rp0);
         if (lane == 0) s_off[wv][64] = len;
         s_thr[wv][lane] = v < a.n ? a.thr[v] : 0u;
+        if constexpr (FAULTS) {
+            const bool dn = v < a.n && outage_down(f.out_off, f.out_from, f.out_to, (uint32_t)v, (uint64_t)a.tick + 1u);
+            s_down[wv][lane] = dn ? 1u : 0u;
+            tdown += dn ? 1u : 0u;
+        }
         s_in[wv][lane] = 0u;
         s_out[wv][lane] = 0u;
         __builtin_amdgcn_wave_barrier();
@@ -112,12 +190,34 @@ __global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) {
                 const uint32_t vv = (uint32_t)c0 + i, to = s_thr[wv][i];
                 const uint32_t mi = m & 15u, mo = m >> 4, mm = mi > mo ? mi : mo;
                 uint32_t oc = 0;
-                for (uint32_t c = 0; c < mm; c++) {
-                    uint32_t x[2];
-                    fanout_draw(a.seed, vv, u, c, a.tick, x);
-                    const uint32_t w_out = vv < u ? x[0] : x[1], w_in = u < vv ? x[0] : x[1];
-                    oc += (c < mo && fanout_pass(w_out, to)) ? 1u : 0u;
-                    sel |= c < mi && fanout_pass(w_in, ti);
+                if constexpr (!FAULTS) {
+                    for (uint32_t c = 0; c < mm; c++) {
+                        uint32_t x[2];
+                        fanout_draw(a.seed, vv, u, c, a.tick, x);
+                        const uint32_t w_out = vv < u ? x[0] : x[1], w_in = u < vv ? x[0] : x[1];
+                        oc += (c < mo && fanout_pass(w_out, to)) ? 1u : 0u;
+                        sel |= c < mi && fanout_pass(w_in, ti);
+                    }
+                } else {
+                    const bool rdown = s_down[wv][i] != 0u;
+                    // a faults-only flood: both thresholds pass whatever the word, so the fanout draw is not made
+                    const bool draw = to != kFanoutAlways || ti != kFanoutAlways;
+                    for (uint32_t c = 0; c < mm; c++) {
+                        uint32_t x[2] = {0u, 0u};
+                        if (draw) draw_rolling(a.seed, kFanoutKey1, vv, u, c, a.tick, x);
+                        const uint32_t w_out = vv < u ? x[0] : x[1], w_in = u < vv ? x[0] : x[1];
+                        oc += (c < mo && fanout_pass(w_out, to)) ? 1u : 0u;  // made and counted, whatever becomes of it
+                        const bool arrives = c < mi && fanout_pass(w_in, ti);  // the copy u -> vv was made
+                        bool lost = false;
+                        if (loss_on) {  // (not per lane "if it arrives": a wave's 64 lanes never all agree on that)
+                            uint32_t y[2];
+                            draw_rolling(f.loss_seed, kLossKey1, vv, u, c, a.tick, y);
+                            lost = loss_pass(u < vv ? y[0] : y[1], f.loss_thr);
+                        }
+                        tdownc += (arrives && rdown) ? 1u : 0u;
+                        tlost += (arrives && !rdown && lost) ? 1u : 0u;
+                        sel |= arrives && !rdown && !lost;
+                    }
                 }
                 if (oc) atomicAdd(&s_out[wv][i], oc);
                 if (sel) atomicAdd(&s_in[wv][i], 1u);
@@ -156,7 +256,25 @@ __global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) {
         if (tin) atomicAdd(st, tin);
         if (tout) atomicAdd(st + 1, tout);
     }
+    if constexpr (FAULTS) {
+        unsigned long long fl = tlost, fc = tdownc, fd = tdown;
+        for (int off = 32; off > 0; off >>= 1) {
+            fl += __shfl_xor(fl, off, 64);
+            fc += __shfl_xor(fc, off, 64);
+            fd += __shfl_xor(fd, off, 64);
+        }
+        if (lane == 0) {
+            unsigned long long* st = a.stat + (blockIdx.x & (kFanoutStatReplicas - 1u)) * kFanoutStatLine;
+            if (fl) atomicAdd(st + 2, fl);
+            if (fc) atomicAdd(st + 3, fc);
+            if (fd) atomicAdd(st + 4, fd);
+        }
+    }
 }
+
+__global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) { fanout_count_body<false>(a, FaultArgs{}); }
+// the count pass with faults: down rows select nothing, a lost copy selects nothing
+__global__ __launch_bounds__(256) void k_fanout_count_faults(FanoutArgs a, FaultArgs f) { fanout_count_body<true>(a, f); }
 
 __global__ __launch_bounds__(256) void k_fanout_compact(FanoutArgs a) {
     const uint32_t lane = threadIdx.x & 63u;

@@ -59,6 +59,10 @@ struct Options {
     std::string reach;                 // reach profile per counted event (GOSSIP_F_REACH)
     uint32_t fanout = 0;               // fanout-limited gossip: expected fanout (0: the reference's flood)
     uint64_t fanoutSeed = 1;           // ... and the seed of its per-(link, tick) draws
+    std::string outages;               // fault injection: outage file, lines "node from_ns to_ns"
+    double loss = 0.0;                 // ... message-loss probability per made Send
+    uint64_t lossSeed = 1;             // ... and the seed of its per-(link, tick) draws
+    bool lossSeedGiven = false;
     bool uniqueIds = false;            // renumber share ids 1..len in event order (ids are only seen-set keys)
 };
 
@@ -73,7 +77,8 @@ void usage() {
                  "                  [--links=F] [--events=F] [--dumpTrace=F] [--netanim=F] [--noPackets]\n"
                  "                  [--log=F|-] [--gpus=N] [--shards=S] [--layout=shards|rows]\n"
                  "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n"
-                 "                  [--fanout=K] [--fanoutSeed=S] [--uniqueIds]\n");
+                 "                  [--fanout=K] [--fanoutSeed=S] [--uniqueIds]\n"
+                 "                  [--outages=F] [--loss=P] [--lossSeed=S]\n");
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -144,16 +149,19 @@ bool parse(int argc, char** argv, Options& o) {
         else if (key == "schedule") { if (!need()) return false; o.schedule = val; }
         else if (key == "reach") { if (!need()) return false; o.reach = val; }
         else if (key == "fanout") { if (!num(d) || d < 1 || d > 4294967295.0) return false; o.fanout = (uint32_t)d; }
-        else if (key == "fanoutSeed") {
+        else if (key == "fanoutSeed" || key == "lossSeed") {
             if (!need()) return false;
             char* end = nullptr;
             errno = 0;
-            o.fanoutSeed = std::strtoull(val.c_str(), &end, 0);
+            (key == "fanoutSeed" ? o.fanoutSeed : o.lossSeed) = std::strtoull(val.c_str(), &end, 0);
+            if (key == "lossSeed") o.lossSeedGiven = true;
             if (errno || end == val.c_str() || *end) {
-                std::fprintf(stderr, "invalid value '%s' for --fanoutSeed\n", val.c_str());
+                std::fprintf(stderr, "invalid value '%s' for --%s\n", val.c_str(), key.c_str());
                 return false;
             }
         }
+        else if (key == "outages") { if (!need()) return false; o.outages = val; }
+        else if (key == "loss") { if (!num(o.loss) || !(o.loss >= 0.0 && o.loss <= 1.0)) return false; }
         else if (key == "uniqueIds") o.uniqueIds = true;
         else {
             std::fprintf(stderr, "unknown option --%s\n", key.c_str());
@@ -225,7 +233,8 @@ struct RowGroup {
 void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank, uint32_t count,
                 const uint8_t* uid, RowGroup* group, const gossip_topology* topo, const gossip_schedule* sched,
                 const std::vector<double>& per_t, bool link_timing, bool want_trace, double mem_limit_mb,
-                uint32_t fanout, uint64_t fanout_seed, Part& out) {
+                uint32_t fanout, uint64_t fanout_seed, const std::vector<gossip_outage>* outages, uint32_t loss_thr,
+                uint64_t loss_seed, Part& out) {
     gossip_config cfg = base;
     cfg.device = device;
     if (!rows && count > 1) {
@@ -251,6 +260,8 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
     // (PPP + IPv4 + TCP with timestamps), 1 ns TcpSocketBase send deferral (gossip.h)
     if (link_timing && (rc = gossip_engine_set_link_timing(eng, 1600, 54, 1))) return fail("link timing", rc);
     if (fanout && (rc = gossip_engine_set_fanout(eng, fanout, fanout_seed))) return fail("fanout", rc);
+    if (outages && (rc = gossip_engine_set_outages(eng, outages->size(), outages->data()))) return fail("outages", rc);
+    if (loss_thr && (rc = gossip_engine_set_link_loss(eng, loss_thr, loss_seed))) return fail("link loss", rc);
     for (double t : per_t)  // Start(): p2pnetwork.cc:201-204
         if ((rc = gossip_engine_add_snapshot(eng, gossip_seconds_to_ns(t)))) return fail("snapshot", rc);
     if ((rc = gossip_engine_set_schedule_obj(eng, sched))) return fail("engine schedule", rc);
@@ -348,6 +359,26 @@ int main(int argc, char** argv) {
         sched = nullptr;
         if (gossip_schedule_from_events(ev.size(), ev.data(), &sched)) return die("schedule renumbering");
     }
+    // ---- fault injection (gossip.h): outages in ticks of --Latency, one loss threshold ----
+    std::vector<gossip_outage> outages;
+    const bool faults = !o.outages.empty() || o.loss > 0.0 || o.lossSeedGiven;
+    if (faults && !o.uniqueIds) {
+        std::fprintf(stderr, "gossip_sim: --outages, --loss and --lossSeed need unique share ids: add --uniqueIds to renumber them\n");
+        return 2;
+    }
+    if (o.loss > 0.0 && o.loss < 1.0 / 4294967296.0) {  // (floor(P * 2^32) = 0 would run without loss, silently)
+        std::fprintf(stderr, "gossip_sim: --loss %g is below the resolution of the 32-bit threshold (2^-32)\n", o.loss);
+        return 2;
+    }
+    if (!o.outages.empty()) {
+        uint64_t m = 0, skipped = 0;
+        if (gossip_outages_load(n, L, o.outages.c_str(), 0, nullptr, &m, nullptr)) return die("outage import");
+        outages.resize(m);
+        if (gossip_outages_load(n, L, o.outages.c_str(), m, outages.data(), &m, &skipped)) return die("outage import");
+        std::printf("outages: %llu interval(s) from %s, %llu line(s) with an empty tick range skipped\n",
+                    (unsigned long long)m, o.outages.c_str(), (unsigned long long)skipped);
+    }
+    const uint32_t loss_thr = o.loss >= 1.0 ? 0xffffffffu : (uint32_t)(o.loss * 4294967296.0);
     if (!o.dumpLinks.empty()) {
         std::vector<uint32_t> a(gossip_topology_num_links(topo)), b(a.size());
         gossip_topology_get_links(topo, a.data(), b.data());
@@ -414,7 +445,8 @@ int main(int argc, char** argv) {
                 // device g runs shards g, g + N, ... (rows: exactly rank g)
                 for (uint32_t r = g; r < count; r += ng)
                     run_engine(cfg, o.device + (int)g, rows, r, count, uid.data(), gp, topo, sched, per_t,
-                               o.linkTiming, want_trace, o.memLimitMB, o.fanout, o.fanoutSeed, parts[r]);
+                               o.linkTiming, want_trace, o.memLimitMB, o.fanout, o.fanoutSeed,
+                               o.outages.empty() ? nullptr : &outages, loss_thr, o.lossSeed, parts[r]);
             });
         for (auto& t : th) t.join();
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();

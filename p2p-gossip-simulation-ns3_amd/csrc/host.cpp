@@ -648,6 +648,39 @@ int gossip_topology_load_links(uint32_t num_nodes, const char* path, gossip_topo
     }
 }
 
+int gossip_outages_load(uint32_t num_nodes, int64_t latency_ns, const char* path, uint64_t cap, gossip_outage* out,
+                        uint64_t* count, uint64_t* skipped) {
+    if (!path || !count || (cap && !out)) return set_error(GOSSIP_EINVAL, "NULL argument");
+    if (latency_ns <= 0) return set_error(GOSSIP_EINVAL, "latency_ns > 0");
+    *count = 0;
+    if (skipped) *skipped = 0;
+    try {
+        std::string text;
+        if (!read_file(path, text)) return set_error(GOSSIP_EINVAL, std::string("cannot read ") + path);
+        uint64_t m = 0, empty = 0;
+        const uint64_t mx[3] = {0xffffffffull, (uint64_t)INT64_MAX - (uint64_t)latency_ns, (uint64_t)INT64_MAX - (uint64_t)latency_ns};
+        const std::string err = parse_rows(text, 3, mx, [&](const uint64_t* v) -> std::string {
+            if (v[0] >= num_nodes) return "node id beyond --numNodes";
+            if (v[1] > v[2]) return "from_ns after to_ns";
+            // down in tick T iff from_ns <= T * L < to_ns
+            const int64_t L = latency_ns, from = ((int64_t)v[1] + L - 1) / L, to = ((int64_t)v[2] + L - 1) / L;
+            if (from >= to) {
+                empty++;
+                return "";
+            }
+            if (m < cap) out[m] = gossip_outage{(uint32_t)v[0], 0u, from, to};
+            m++;
+            return "";
+        });
+        if (!err.empty()) return set_error(GOSSIP_EINVAL, std::string(path) + ": " + err);
+        *count = m;
+        if (skipped) *skipped = empty;
+        return GOSSIP_OK;
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed reading outages");
+    }
+}
+
 int gossip_schedule_load_events(uint32_t num_nodes, const char* path, gossip_schedule** out) {
     if (!out || !path) return set_error(GOSSIP_EINVAL, "NULL argument");
     *out = nullptr;

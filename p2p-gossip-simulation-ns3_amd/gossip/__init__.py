@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_get_reach_totals", "gossip_engine_get_reach",
     "gossip_engine_set_fanout", "gossip_engine_set_forward_thresholds", "gossip_fanout_selected",
     "gossip_engine_get_fanout_counters",
+    "gossip_engine_set_outages", "gossip_engine_set_link_loss", "gossip_fault_lost",
+    "gossip_engine_get_fault_counters", "gossip_outages_load",
 )
 
 # launch ledger (gossip.h): kernel ids and k_pull's template flags
@@ -136,6 +138,20 @@ class gossip_fanout_counters(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64), ("selected_in", C.c_uint64), ("selected_out", C.c_uint64),
         ("entries", C.c_uint64), ("ms", C.c_double), ("bytes", C.c_uint64),
+    ]
+
+
+class gossip_outage(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("pad", C.c_uint32), ("tick_from", C.c_int64), ("tick_to", C.c_int64)]
+
+
+OUTAGE_DTYPE = np.dtype([("node", "<u4"), ("pad", "<u4"), ("tick_from", "<i8"), ("tick_to", "<i8")])
+
+
+class gossip_fault_counters(C.Structure):
+    _fields_ = [
+        ("launches", C.c_uint64), ("down_node_ticks", C.c_uint64), ("lost_copies", C.c_uint64),
+        ("down_copies", C.c_uint64), ("dropped_generations", C.c_uint64),
     ]
 
 
@@ -264,6 +280,11 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_set_forward_thresholds": (C.c_int, [P, P, u64]),
         "gossip_fanout_selected": (C.c_int, [u64, u32, u32, u32, i64, u32]),
         "gossip_engine_get_fanout_counters": (C.c_int, [P, C.POINTER(gossip_fanout_counters)]),
+        "gossip_engine_set_outages": (C.c_int, [P, u64, P]),
+        "gossip_engine_set_link_loss": (C.c_int, [P, u32, u64]),
+        "gossip_fault_lost": (C.c_int, [u64, u32, u32, u32, i64, u32]),
+        "gossip_engine_get_fault_counters": (C.c_int, [P, C.POINTER(gossip_fault_counters)]),
+        "gossip_outages_load": (C.c_int, [u32, i64, C.c_char_p, u64, P, C.POINTER(u64), C.POINTER(u64)]),
         "gossip_engine_destroy": (None, [P]),
         "gossip_format_statistics": (i64, [u32, P, P, P, P, P, P, P, C.c_char_p, u64]),
         "gossip_format_periodic": (i64, [C.c_double, u32, u64, u64, u64, C.c_char_p, u64]),
@@ -451,6 +472,44 @@ def fanout_selected(seed: int, sender: int, receiver: int, copy: int, tick: int,
                                                       int(thr)))
 
 
+def fault_lost(seed: int, sender: int, receiver: int, copy: int, tick: int, loss_thr: int) -> bool:
+    """The message-loss rule (gossip.h, gossip_fault_lost): is the Send sender -> receiver, copy `copy`,
+    made in tick `tick` lost under the threshold `loss_thr`?  No engine, no device."""
+    return bool(load_library().gossip_fault_lost(int(seed), int(sender), int(receiver), int(copy), int(tick),
+                                                 int(loss_thr)))
+
+
+def loss_threshold(p: float) -> int:
+    """The loss threshold of a loss probability: floor(p * 2^32), 0xffffffff from p = 1 (always)."""
+    if not 0.0 <= p <= 1.0:
+        raise GossipError("loss_threshold: a probability in [0, 1]", E_INVAL)
+    return min(int(p * 4294967296.0), 0xFFFFFFFF)
+
+
+def crash_outages(n: int, fraction: float, tick_from: int, tick_to: int | None = None, seed: int = 1):
+    """(nodes, tick_from, tick_to) for Engine.set_outages: a random `fraction` of the n nodes (numpy's
+    default generator, `seed`) is down from tick_from -- to tick_to, or for the rest of the run.  A
+    convenience only; the nodes are returned in ascending order."""
+    if not 0.0 <= fraction <= 1.0:
+        raise GossipError("crash_outages: a fraction in [0, 1]", E_INVAL)
+    k = int(round(fraction * n))
+    nodes = np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.uint32)
+    end = np.iinfo(np.int64).max if tick_to is None else int(tick_to)
+    return nodes, np.full(k, int(tick_from), np.int64), np.full(k, end, np.int64)
+
+
+def load_outages(n: int, latency_ns: int, path: str):
+    """An outage file (lines "node from_ns to_ns"; gossip.h, gossip_outages_load) as (nodes, tick_from,
+    tick_to, skipped): the arrays for Engine.set_outages and the number of lines whose tick range is empty."""
+    lib = load_library()
+    count, skipped = C.c_uint64(0), C.c_uint64(0)
+    _check(lib.gossip_outages_load(int(n), int(latency_ns), str(path).encode(), 0, None, C.byref(count), None), "load outages")
+    o = np.zeros(count.value, OUTAGE_DTYPE)
+    _check(lib.gossip_outages_load(int(n), int(latency_ns), str(path).encode(), o.size, _vp(o), C.byref(count),
+                                   C.byref(skipped)), "load outages")
+    return o["node"].copy(), o["tick_from"].copy(), o["tick_to"].copy(), int(skipped.value)
+
+
 def unique_ids(ev: np.ndarray) -> np.ndarray:
     """A copy of the events with share ids renumbered 1..len in event order.  Ids are only seen-set
     keys, so a schedule whose ids collide (n > 128,849) runs in the modes that need unique ids
@@ -600,6 +659,31 @@ class Engine:
     def fanout_counters(self) -> gossip_fanout_counters:
         c = gossip_fanout_counters()
         _check(load_library().gossip_engine_get_fanout_counters(self._h, C.byref(c)), "fanout counters")
+        return c
+
+    def set_outages(self, nodes, tick_from, tick_to):
+        """Node outages (gossip.h, gossip_engine_set_outages): node nodes[k] is down in the ticks
+        [tick_from[k], tick_to[k]) (absolute ticks, as first_tick counts them; scalars broadcast).  After
+        the graph, before the schedule; a second call replaces the first, empty arrays clear."""
+        nodes, tick_from, tick_to = np.broadcast_arrays(np.asarray(nodes, np.int64).ravel(), np.asarray(tick_from, np.int64),
+                                                        np.asarray(tick_to, np.int64))
+        if nodes.size and (nodes.min() < 0 or nodes.max() > 0xFFFFFFFF):
+            raise GossipError("set_outages: node ids are 32-bit", E_INVAL)
+        o = np.zeros(nodes.size, OUTAGE_DTYPE)
+        o["node"], o["tick_from"], o["tick_to"] = nodes, tick_from, tick_to
+        _check(load_library().gossip_engine_set_outages(self._h, o.size, _vp(o)), "set outages")
+
+    def set_link_loss(self, p_or_thr, seed: int = 1):
+        """Message loss (gossip.h, gossip_engine_set_link_loss): a float is a probability (loss_threshold),
+        an int the 32-bit threshold itself; 0 switches loss off.  After the graph, before the schedule."""
+        thr = loss_threshold(p_or_thr) if isinstance(p_or_thr, (float, np.floating)) else int(p_or_thr)
+        if not 0 <= thr <= 0xFFFFFFFF:
+            raise GossipError("set_link_loss: a 32-bit threshold", E_INVAL)
+        _check(load_library().gossip_engine_set_link_loss(self._h, thr, int(seed)), "set link loss")
+
+    def fault_counters(self) -> gossip_fault_counters:
+        c = gossip_fault_counters()
+        _check(load_library().gossip_engine_get_fault_counters(self._h, C.byref(c)), "fault counters")
         return c
 
     def set_schedule(self, ev: np.ndarray):
