@@ -301,9 +301,8 @@ uint32_t gossip_share_message_length(uint32_t origin, uint32_t share_id, int64_t
  * latency, cut, thr, seed): no tuning option, tile layout or share sharding changes it (share shards
  * add up to the single engine).
  *   gossip_engine_set_fanout(k): thr[u] = 0xffffffff if deg(u) <= k, else floor(k * 2^32 / deg(u)),
- * deg = the sum of multiplicities of u's row: an EXPECTED fanout of k, binomial.  An exact k-subset
- * is not offered: it needs v's position in u's list and u's degree per entry, two more random
- * gathers per entry and tick.
+ * deg = the sum of multiplicities of u's row: an EXPECTED fanout of k, binomial.  For exactly k Sends
+ * per tick see gossip_engine_set_fanout_exact below.
  *   gossip_engine_set_forward_thresholds: thr[n] given by the caller.
  * Both: after the graph and before the schedule (GOSSIP_ESTATE otherwise); every buffer of the mode
  * is allocated here.  Share ids must be unique (gossip_engine_set_schedule returns GOSSIP_EINVAL
@@ -319,6 +318,47 @@ int gossip_engine_set_fanout(gossip_engine* e, uint32_t fanout /* >= 1 */, uint6
 int gossip_engine_set_forward_thresholds(gossip_engine* e, const uint32_t* thr /* n */, uint64_t seed);
 int gossip_fanout_selected(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy,
                            int64_t tick, uint32_t thr);
+
+/* Exact-k fanout: every sender pushes to exactly k of its peer copies per tick.  For sender u in tick T,
+ * u's out-copies are the pairs (v, c) with c < mult(u -> v), D is their number (the sum of the
+ * multiplicities of u's row) and k[u] is the node's fanout count:
+ *     lo = min(u, v), hi = max(u, v)
+ *     x  = Philox4x32-10(counter = (lo, hi, (uint32)T, c),
+ *                        key = (seed & 0xffffffff, (seed >> 32) ^ 0x46414E4B))            "FANK"
+ *     w(u->v,c,T) = (u < v) ? (uint64)x[0] << 32 | x[1]  :  (uint64)x[2] << 32 | x[3]
+ *     q(u,T)      = the k[u]-th smallest (with multiplicity) of u's D draws
+ *     selected    = k[u] > 0  &&  (D <= k[u]  ||  w <= q(u,T))
+ * Each out-copy gets an i.i.d. 64-bit draw and the k smallest are sent: a uniform k-subset, chosen by an
+ * order statistic, so a receiver needs only its sender's q, never its position in the sender's list.
+ *   - One Philox call serves both directions of a link.  The key constant is new: the exact draws are
+ *     independent of the binomial draws and of the loss draws.
+ *   - A sender with D > k[u] makes exactly k[u] Sends in every tick in which it sends anything.  Two draws
+ *     tie at the k-th value with probability about 2^-64 per pair; then all tied copies are selected, and
+ *     the out-count is counted, not assumed, so sent stays consistent.
+ *   - The draw belongs to (sender, receiver, copy, tick), not to a share, as in binomial mode: everything
+ *     a node sends in one tick goes to the same k copies.  Ticks, sent, edge_events, recv, the trace,
+ *     snapshots, reach and the cut keep the meaning they have in fanout mode.
+ *   - The result is a pure function of (graph, events, latency, cut, k[], seed), and of the fault inputs if
+ *     set: no tuning option, tile layout or share sharding changes it.
+ *   - Faults compose as with the binomial rule: the exact rule decides whether a Send is made, outages and
+ *     loss whether a made Send arrives; the loss key and seed are untouched.
+ *   gossip_engine_set_fanout_exact(k): k[u] = k at every node.
+ *   gossip_engine_set_fanout_counts: k[n] given by the caller; a count of 0 makes a silent node.
+ * Both stand where the binomial setters stand (after the graph, before the schedule), refuse what they
+ * refuse with the same messages, and need unique share ids; among the four fanout setters the last call
+ * before the schedule wins, and the fault setters compose with them in either order.  A node that must
+ * select (D > k[u]) takes k[u] <= 32: above that the call is GOSSIP_EINVAL and names the node.  32 is
+ * enough because fanouts in practice are about ln n (ln 10^9 = 21), and a node with D <= k[u] sends every
+ * copy and selects nothing, at any k.  The tables of the mode (16 B per node) are allocated here.  Every
+ * tick runs one more pass over the rows in front of the count pass (k_fanout_kth, csrc/fanout_kernel.h:
+ * each sender's q and out-count), and the count pass gathers 8 B per entry.
+ *   gossip_fanout_exact_row: the rule itself for one sender's `count` out-copies (receiver[i], copy[i]):
+ * selected[i] = 1 / 0 and, if draws is not NULL, draws[i] = w.  Any k; needs no engine and no device. */
+int gossip_engine_set_fanout_exact(gossip_engine* e, uint32_t fanout /* >= 1 */, uint64_t seed);
+int gossip_engine_set_fanout_counts(gossip_engine* e, const uint32_t* k /* n */, uint64_t seed);
+int gossip_fanout_exact_row(uint64_t seed, uint32_t sender, uint32_t count, const uint32_t* receiver,
+                            const uint32_t* copy, uint32_t k, int64_t tick, uint8_t* selected,
+                            uint64_t* draws /* may be NULL */);
 typedef struct gossip_fanout_counters {
     uint64_t launches;      /* ticks whose Sends were selected (count pass + scan + compact pass) */
     uint64_t selected_in;   /* peer-list entries kept, summed over ticks                          */
@@ -326,9 +366,12 @@ typedef struct gossip_fanout_counters {
     uint64_t entries;       /* peer-list entries examined, summed over ticks                      */
     double ms;              /* summed HIP-event time of those launches (GOSSIP_F_TIMING)          */
     uint64_t bytes;         /* bytes they had to move (model: 9 B + 2 bits per entry, 68 B per
-                               node, 8 B per kept entry)                                          */
+                               node, 8 B per kept entry; exact-k: 13 B + 2 bits per entry, 88 B
+                               per node, 5 B per entry of a selecting node's row, 8 B per kept
+                               entry)                                                             */
 } gossip_fanout_counters;
 /* Since the last gossip_engine_reset_timing; zeros on an engine without fanout and without faults.
+ * In exact-k mode the same fields: launches counts ticks, ms includes k_fanout_kth.
  * On a faults-only engine (gossip_engine_set_outages / _set_link_loss and no fanout setter) these are
  * the thinning passes of the fault mode: every threshold is 0xffffffff there. */
 int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* c);
@@ -635,7 +678,9 @@ int gossip_engine_reset_timing(gossip_engine* e);
  *             counter in LDS, 2 k_reach_slots with more than 8 write-sparse tiles (the 8 oldest
  *             tiles' counters in LDS, a global atomic per entry of the others); GOSSIP_K_FANOUT: 1 the
  *             count pass, 2 the compact pass, 3 the count pass with faults (k_fanout_count_faults, in place
- *             of 1 on an engine with outages or loss; strided: a wave looped over several 64-node chunks);
+ *             of 1 on an engine with outages or loss; strided: a wave looped over several 64-node chunks),
+ *             exact-k: 4 the k-th-draw pass (k_fanout_kth), 5 the exact count pass, 6 the exact count pass
+ *             with faults (5 / 6 in place of 1 / 3; the compact pass is 2 in every mode);
  *             0 otherwise
  *   launches  launches of that variant
  *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's

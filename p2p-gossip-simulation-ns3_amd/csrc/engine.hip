@@ -1050,7 +1050,16 @@ struct gossip_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_fanout;
     double fanout_ms_done = 0.0;
     int fanout_launch(int64_t t);      // tick_step_b: the selection of tick t, for the pull of t + 1
-    int fanout_setup(const uint32_t* thr, uint64_t seed);
+    int fanout_setup(const uint32_t* thr, uint64_t seed, const uint32_t* exact_k = nullptr);
+    // ---- exact-k fanout (gossip_engine_set_fanout_exact / _set_fanout_counts): k_fanout_kth in front of
+    // the exact count pass; its three tables are allocated by those setters and by nothing else
+    bool fanout_exact = false;
+    uint32_t exact_slots = 0;          // 8 or 32: the k_fanout_kth instantiation (largest k of a selecting node)
+    uint32_t *d_xk = nullptr, *d_xout = nullptr;  // n each: k of a selecting node (else 0); out-count of the others
+    uint64_t* d_xbound = nullptr;      // n: the tick's bounds
+    uint64_t exact_bytes = 0;          // device bytes of the three (in device_bytes)
+    uint64_t exact_drawn = 0;          // peer-list entries of the selecting nodes: what k_fanout_kth walks per tick
+    int fanout_exact_setup(const uint32_t* k, uint64_t seed);
     void fanout_free();                // every buffer above (a setter call that failed half-way, the destructor)
     bool fanout_allocated = false;     // the setter's allocations all succeeded
     // ---- fault injection (gossip_engine_set_outages / _set_link_loss): a second reason to drop an entry
@@ -1211,6 +1220,7 @@ gossip_engine::~gossip_engine() {
         hipEventDestroy(p.second);
     }
     fanout_free();
+    hipFree(d_xk); hipFree(d_xout); hipFree(d_xbound);
     hipFree(d_out_off); hipFree(d_out_from); hipFree(d_out_to);
     if (comm && !aborted.load()) ncclCommDestroy(comm);  // (an aborted communicator is already freed)
     for (int k = 0; k < kRing; k++) {
@@ -1678,7 +1688,7 @@ int gossip_engine::alloc_device() {
     }
     device_bytes = 2 * bm + bm_seen + (d_sat ? 24ull : 16ull) * n * ntw + (uint64_t)n * 20 + nnz * 4 + ((uint64_t)n + 1) * 8 + 2ull * stride * 8 + slot_bytes +
                    kRing * ((uint64_t)stride * sizeof(WordCtl) + (uint64_t)bcap * sizeof(Birth) + pcap * 4);
-    device_bytes += fanout_bytes + outage_bytes;  // (allocated by the fanout / fault setters; 0 without one)
+    device_bytes += fanout_bytes + outage_bytes + exact_bytes;  // (allocated by the fanout / fault setters; 0 without one)
     if (dense) {
         const uint64_t ft = (uint64_t)stride * 8 * n_pad;
         snz_nstw = (n_pad / kStageK + 63u) / 64u;
@@ -3669,7 +3679,7 @@ void gossip_engine::fanout_free() {
     fscan_tmp_bytes = 0;
 }
 
-int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed) {
+int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed, const uint32_t* exact_k) {
     HIP_TRY(hipSetDevice(device));
     std::vector<uint32_t> in_thr(nnz);
     std::vector<uint8_t> em(nnz);
@@ -3685,7 +3695,8 @@ int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed) {
             if (mo > 15u || mi > 15u)
                 return set_error(GOSSIP_EINVAL, "fanout: multiplicity above 15 at row " + std::to_string(v) + ", col " + std::to_string(u));
             in_thr[j] = thr[u];
-            em[j] = (uint8_t)(mi | (mo << 4));
+            // (exact-k: a silent sender has no in-copies anywhere -- the bound table has no "none", fanout_kernel.h)
+            em[j] = (uint8_t)((exact_k && exact_k[u] == 0u ? 0u : mi) | (mo << 4));
         }
     if (!fanout_allocated) {
         fanout_free();  // (what an earlier call that failed half-way left)
@@ -3724,7 +3735,55 @@ int gossip_engine::fanout_setup(const uint32_t* thr, uint64_t seed) {
     }
     HIP_TRY(hipStreamSynchronize(stream));  // (the host arrays go out of scope)
     fanout = true;
+    fanout_exact = false;  // (fanout_exact_setup sets it after this: the last setter wins)
     fanout_seed = seed;
+    return GOSSIP_OK;
+}
+
+// Exact-k fanout on top of the buffers above: per node, k if it must select (D > k >= 1) and the out-count
+// if it need not (D, or 0 at a silent node); the bound table of the ticks.  D = h_peers: the sum of the row's
+// multiplicities.
+int gossip_engine::fanout_exact_setup(const uint32_t* k, uint64_t seed) {
+    HIP_TRY(hipSetDevice(device));
+    std::vector<uint32_t> xk(n), xout(n);
+    uint32_t kmax = 0;
+    uint64_t drawn = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        const uint32_t D = h_peers[v];
+        const bool selects = k[v] != 0u && D > k[v];
+        if (selects && k[v] > gossip::kFanoutExactMax)
+            return set_error(GOSSIP_EINVAL, "fanout: node " + std::to_string(v) + " has " + std::to_string(D) + " peer copies and a fanout count of " +
+                                                std::to_string(k[v]) + ": a node that must select takes at most " +
+                                                std::to_string(gossip::kFanoutExactMax));
+        xk[v] = selects ? k[v] : 0u;
+        xout[v] = selects || k[v] == 0u ? 0u : D;
+        if (selects) {
+            kmax = std::max(kmax, k[v]);
+            drawn += (uint64_t)(h_rowptr[v + 1] - h_rowptr[v]);
+        }
+    }
+    std::vector<uint32_t> thr(n, gossip::kFanoutAlways);  // (not read by the exact passes)
+    if (int rc = fanout_setup(thr.data(), seed, k)) return rc;
+    if (!d_xbound) {
+        const size_t n1 = (size_t)n + 1;
+        uint32_t *a = nullptr, *b = nullptr;
+        uint64_t* c = nullptr;
+        if (hipMalloc(&a, n1 * 4) != hipSuccess || hipMalloc(&b, n1 * 4) != hipSuccess || hipMalloc(&c, n1 * 8) != hipSuccess) {
+            hipFree(a); hipFree(b); hipFree(c);
+            (void)hipGetLastError();
+            return set_error(GOSSIP_ENOMEM, "fanout: device allocation failed");
+        }
+        d_xk = a; d_xout = b; d_xbound = c;
+        exact_bytes = n1 * 16;
+        device_bytes += exact_bytes;
+    }
+    if (n) {
+        HIP_TRY(hipMemcpy(d_xk, xk.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_xout, xout.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    exact_slots = kmax <= 8u ? 8u : 32u;
+    exact_drawn = drawn;
+    fanout_exact = true;
     return GOSSIP_OK;
 }
 
@@ -3795,7 +3854,27 @@ int gossip_engine::fanout_launch(int64_t t) {
         HIP_TRY(hipEventRecord(e0, stream));
     }
     HIP_TRY(hipMemsetAsync(d_fbitmap, 0, ((size_t)(nnz + 63) / 64 + 1) * 8, stream));
-    if (faults()) {  // outages or loss: the count pass that also drops down rows and lost copies
+    if (fanout_exact) {  // the senders' bounds and the out side first, then the count pass against the bounds
+        gossip::ExactArgs x;
+        x.kx = d_xk; x.xout = d_xout; x.bound = d_xbound;
+        if (exact_slots == 8u) gossip::k_fanout_kth<8><<<grid, 256, 0, stream>>>(a, x);
+        else gossip::k_fanout_kth<32><<<grid, 256, 0, stream>>>(a, x);
+        HIP_TRY(hipGetLastError());
+        ledger.add(gossip::LK_FANOUT, 4u, strided);
+        if (faults()) {
+            gossip::FaultArgs f;
+            f.out_off = d_out_off; f.out_from = d_out_from; f.out_to = d_out_to;
+            f.loss_seed = loss_seed; f.loss_thr = loss_thr;
+            gossip::k_fanout_count_exact_faults<<<grid, 256, 0, stream>>>(a, f, x);
+            HIP_TRY(hipGetLastError());
+            ledger.add(gossip::LK_FANOUT, 6u, strided);
+            fault_launches++;
+        } else {
+            gossip::k_fanout_count_exact<<<grid, 256, 0, stream>>>(a, x);
+            HIP_TRY(hipGetLastError());
+            ledger.add(gossip::LK_FANOUT, 5u, strided);
+        }
+    } else if (faults()) {  // outages or loss: the count pass that also drops down rows and lost copies
         gossip::FaultArgs f;
         f.out_off = d_out_off; f.out_from = d_out_from; f.out_to = d_out_to;
         f.loss_seed = loss_seed; f.loss_thr = loss_thr;
@@ -4646,6 +4725,49 @@ int gossip_engine_set_fanout(gossip_engine* e, uint32_t fanout, uint64_t seed) {
     }
 }
 
+static int fanout_exact_set(gossip_engine* e, const uint32_t* k, uint64_t seed) {
+    try {
+        if (int rc = e->fanout_exact_setup(k, seed)) return rc;
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+    if (e->dense) {  // AUTO had resolved to DENSE: fanout runs the CSR pull
+        e->dense = false;
+        hipFree(e->d_Ab);
+        e->d_Ab = nullptr;
+    }
+    return GOSSIP_OK;
+}
+
+int gossip_engine_set_fanout_counts(gossip_engine* e, const uint32_t* k, uint64_t seed) {
+    if (int rc = fanout_check(e)) return rc;
+    if (!k) return set_error(GOSSIP_EINVAL, "NULL argument");
+    return fanout_exact_set(e, k, seed);
+}
+
+int gossip_engine_set_fanout_exact(gossip_engine* e, uint32_t fanout, uint64_t seed) {
+    if (int rc = fanout_check(e)) return rc;
+    if (fanout < 1) return set_error(GOSSIP_EINVAL, "fanout >= 1");
+    try {
+        std::vector<uint32_t> k(e->n, fanout);
+        return fanout_exact_set(e, k.data(), seed);
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+}
+
+int gossip_fanout_exact_row(uint64_t seed, uint32_t sender, uint32_t count, const uint32_t* receiver, const uint32_t* copy, uint32_t k,
+                            int64_t tick, uint8_t* selected, uint64_t* draws) {
+    if (count && (!receiver || !copy || !selected)) return set_error(GOSSIP_EINVAL, "NULL argument");
+    try {
+        std::vector<uint64_t> work((size_t)count + std::min(k, count));
+        gossip::fanout_exact_row(seed, sender, count, receiver, copy, k, (uint32_t)tick, selected, draws, work.data());
+    } catch (const std::bad_alloc&) {
+        return set_error(GOSSIP_ENOMEM, "host allocation failed");
+    }
+    return GOSSIP_OK;
+}
+
 int gossip_fanout_selected(uint64_t seed, uint32_t sender, uint32_t receiver, uint32_t copy, int64_t tick, uint32_t thr) {
     return gossip::fanout_selected(seed, sender, receiver, copy, (uint32_t)tick, thr) ? 1 : 0;
 }
@@ -4751,6 +4873,13 @@ int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* 
     c->bytes = e->fanout_launches * (nnz * 9 + 2 * ((nnz + 63) / 64 + 1) * 8 + nnz / 8 + n * (8 + 4 + 16 + 8 + 4 + 16) + n * 12 +
                                      (n + 63) / 64 * 16) +
                c->selected_in * 8;
+    // exact-k on top: k_fanout_kth reads two pointers, k, the fixed out-count, recv, gen and their copies per
+    // node (8 + 4 + 4 + 16), writes the bound and the copies (8 + 8) and at most sent (16), and walks col and
+    // emult (5 B) of the selecting nodes' rows; the count pass gathers a bound (8 B) per entry and, against
+    // the model above, reads neither in_thr (4 B per entry) nor thr, recv, gen and the copies, and writes no
+    // copies and no sent (4 + 16 + 8 + 16 per node)
+    if (e->fanout_exact)
+        c->bytes += e->fanout_launches * (n * 64 + e->exact_drawn * 5 + nnz * 8) - e->fanout_launches * (nnz * 4 + n * 44);
     return GOSSIP_OK;
 }
 

@@ -95,6 +95,105 @@ GOSSIP_HD bool outage_down(const uint32_t* off, const uint32_t* from, const uint
     return lo > first && t < to[lo - 1u];
 }
 
+// ---- exact-k fanout (gossip.h, gossip_engine_set_fanout_exact / _set_fanout_counts) ---------------
+// Sender u with D out-copies and fanout count k[u] in tick T: every out-copy (v, c) gets the 64-bit draw
+//     x = Philox4x32-10(counter = (lo, hi, (uint32)T, c), key = (seed & 0xffffffff, (seed >> 32) ^ "FANK"))
+//     w(u -> v, c, T) = u < v ? x[0] << 32 | x[1] : x[2] << 32 | x[3]
+// and the copies with the k[u] smallest draws are sent: q(u, T) = the k[u]-th smallest of the D draws,
+//     selected = k[u] > 0 && (D <= k[u] || w <= q(u, T))
+// i.i.d. draws ranked: a uniform k-subset.  Draws that tie at q are all selected (the out-count is counted).
+// Per tick T, in front of the count pass:
+//   k_fanout_kth      one lane per row u.  A node that must select (D > k[u] >= 1) walks its row, draws once
+//                     per out-copy and keeps the k smallest in LDS ([slot][lane]: conflict-free), the largest
+//                     of them and its slot in registers; a draw below the largest replaces it and costs one
+//                     re-scan of the k slots (about k ln(D / k) of them per row).  It writes bound[u] = q and
+//                     owns the out side: sent_f[u] += out-count x (first receptions + generations of u in T),
+//                     and rolls recv_prev / gen_prev (the exact count pass does not touch them).  A node that
+//                     sends every copy (D <= k[u]) or none (k[u] = 0) makes no draw: bound = all-ones, out-count
+//                     from the setter's table.
+//   count pass        fanout_count_body<FAULTS, true>: the in side is c < mi && w(u -> v, c, T) <= bound[u],
+//                     bound gathered by col[j] (n x 8 B: cache-resident).  The 2^64 + 1 predicates "none" and
+//                     "w <= q" do not fit 64 bits: a silent sender (k[u] = 0) is taken out at the setter, which
+//                     writes in-multiplicity 0 for its entries, so the table needs no "none"; "all" is
+//                     2^64 - 1, which w <= bound passes exactly.
+//   scan, k_fanout_compact   unchanged.
+constexpr uint32_t kFanoutExactKey1 = 0x46414E4Bu;  // "FANK": xor of the second key word of the exact draw
+constexpr uint32_t kFanoutExactMax = 32;            // largest k at a node that must select (LDS slots per lane)
+constexpr uint64_t kFanoutExactAll = ~0ull;         // bound: every copy passes
+
+// the draw's four words -> w of direction u -> v
+GOSSIP_HD uint64_t fanout_exact_word(uint32_t u, uint32_t v, const uint32_t x[4]) {
+    return u < v ? ((uint64_t)x[0] << 32 | x[1]) : ((uint64_t)x[2] << 32 | x[3]);
+}
+// w(u -> v, c, T)
+GOSSIP_HD uint64_t fanout_exact_draw(uint64_t seed, uint32_t u, uint32_t v, uint32_t c, uint32_t tick) {
+    uint32_t ctr[4] = {u < v ? u : v, u < v ? v : u, tick, c};
+    philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32) ^ kFanoutExactKey1);
+    return fanout_exact_word(u, v, ctr);
+}
+// THE compare: plain <= on all 64 bits, so exact at w = 0 (passes every bound), at w = 2^64 - 1 (passes
+// only the bound 2^64 - 1) and for kFanoutExactAll
+GOSSIP_HD bool fanout_exact_pass(uint64_t w, uint64_t bound) { return w <= bound; }
+// The k smallest of a stream of draws: keep[] holds them (any order), mx the largest of them, at, its slot,
+// ties the draws seen outside keep[] that equal mx.  keep[i * stride] is slot i (the kernel's [slot][lane]).
+struct FanoutExactTop {
+    uint64_t mx;
+    uint32_t at, have, ties;
+};
+GOSSIP_HD void fanout_exact_push(FanoutExactTop& s, uint64_t* keep, uint32_t stride, uint32_t k, uint64_t w) {
+    if (s.have < k) {
+        keep[(size_t)s.have * stride] = w;
+        if (s.have == 0 || w > s.mx) {
+            s.mx = w;
+            s.at = s.have;
+        }
+        s.have++;
+    } else if (w < s.mx) {
+        const uint64_t old = s.mx;
+        keep[(size_t)s.at * stride] = w;
+        uint64_t m = 0;
+        uint32_t at = 0;
+        for (uint32_t i = 0; i < k; i++) {
+            const uint64_t x = keep[(size_t)i * stride];
+            if (x >= m) {
+                m = x;
+                at = i;
+            }
+        }
+        s.mx = m;
+        s.at = at;
+        s.ties = m == old ? s.ties + 1u : 0u;  // the evicted draw: still at the bound, or above it with every earlier tie
+    } else if (w == s.mx) {
+        s.ties++;
+    }
+}
+// The bound of a sender with the draws w[0 .. D) and the count k: q = the k-th smallest (with multiplicity)
+// if it must select (D > k >= 1), kFanoutExactAll if D <= k; *count = the copies sent (k, or more when draws
+// tie at q; D; 0 at k = 0, where the bound means nothing: no copy is sent).  keep: min(k, D) words of scratch.
+GOSSIP_HD uint64_t fanout_exact_bound(const uint64_t* w, uint32_t D, uint32_t k, uint64_t* keep, uint32_t* count) {
+    if (k == 0u || D <= k) {
+        *count = k ? D : 0u;
+        return kFanoutExactAll;
+    }
+    FanoutExactTop s = {0ull, 0u, 0u, 0u};
+    for (uint32_t i = 0; i < D; i++) fanout_exact_push(s, keep, 1u, k, w[i]);
+    *count = s.have + s.ties;
+    return s.mx;
+}
+// THE definition of the rule for one sender's D out-copies (receiver[i], copy[i]): selected[i], and the draws
+// if asked for.  Returns the number selected.  Any k; D <= k and k = 0 make no selection.
+inline uint32_t fanout_exact_row(uint64_t seed, uint32_t sender, uint32_t D, const uint32_t* receiver, const uint32_t* copy,
+                                 uint32_t k, uint32_t tick, uint8_t* selected, uint64_t* draws, uint64_t* work /* D + min(k, D) */) {
+    for (uint32_t i = 0; i < D; i++) {
+        work[i] = fanout_exact_draw(seed, sender, receiver[i], copy[i], tick);
+        if (draws) draws[i] = work[i];
+    }
+    uint32_t count = 0;
+    const uint64_t bound = fanout_exact_bound(work, D, k, work + D, &count);
+    for (uint32_t i = 0; i < D; i++) selected[i] = (k && fanout_exact_pass(work[i], bound)) ? 1 : 0;
+    return count;
+}
+
 #if defined(__HIPCC__)
 
 // 128-B lines of [selected_in, selected_out, lost_copies, down_copies, down_node_ticks] (the last three: faults)
@@ -149,9 +248,16 @@ struct FaultArgs {
     uint32_t loss_thr;         // 0: no loss, and no loss draw
 };
 
-template <bool FAULTS>
-__device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const FaultArgs f) {
-    __shared__ uint32_t s_off[4][65], s_thr[4][64], s_in[4][64], s_out[4][64];
+// exact-k fanout: what k_fanout_kth and the exact count passes take on top of FanoutArgs
+struct ExactArgs {
+    const uint32_t* kx;    // per node: k[u] if u must select (D > k[u] >= 1), else 0
+    const uint32_t* xout;  // per node: the out-count of a node that does not select (D, or 0 if silent)
+    uint64_t* bound;       // per node: q(u, T), or kFanoutExactAll; written by k_fanout_kth each tick
+};
+
+template <bool FAULTS, bool EXACT>
+__device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const FaultArgs f, const ExactArgs xa) {
+    __shared__ uint32_t s_off[4][65], s_thr[EXACT ? 1 : 4][EXACT ? 1 : 64], s_in[4][64], s_out[EXACT ? 1 : 4][EXACT ? 1 : 64];
     __shared__ uint32_t s_down[FAULTS ? 4 : 1][FAULTS ? 64 : 1];  // (faults) the row is down in tick + 1
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -165,14 +271,14 @@ __device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const Faul
         const uint32_t len = (uint32_t)(a.rowptr[c0 + 64u < a.n ? c0 + 64u : a.n] - rp0);
         s_off[wv][lane] = (uint32_t)(a.rowptr[v < a.n ? v : a.n] - rp0);
         if (lane == 0) s_off[wv][64] = len;
-        s_thr[wv][lane] = v < a.n ? a.thr[v] : 0u;
+        if constexpr (!EXACT) s_thr[wv][lane] = v < a.n ? a.thr[v] : 0u;
         if constexpr (FAULTS) {
             const bool dn = v < a.n && outage_down(f.out_off, f.out_from, f.out_to, (uint32_t)v, (uint64_t)a.tick + 1u);
             s_down[wv][lane] = dn ? 1u : 0u;
             tdown += dn ? 1u : 0u;
         }
         s_in[wv][lane] = 0u;
-        s_out[wv][lane] = 0u;
+        if constexpr (!EXACT) s_out[wv][lane] = 0u;
         __builtin_amdgcn_wave_barrier();
         const uint32_t head = (uint32_t)(rp0 & 63);
         const int64_t j0 = rp0 - head;  // 64-aligned
@@ -182,15 +288,32 @@ __device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const Faul
             if (jj >= head && jj < head + len) {
                 const uint32_t rel = jj - head;
                 const int64_t j = j0 + jj;
-                const uint32_t u = (uint32_t)a.col[j], ti = a.in_thr[j], m = a.emult[j];
+                const uint32_t u = (uint32_t)a.col[j], ti = EXACT ? 0u : a.in_thr[j], m = a.emult[j];
                 uint32_t i = 0;  // the row: the last i in [0, 63] with s_off[i] <= rel
 #pragma unroll
                 for (uint32_t s = 32; s; s >>= 1)
                     if (s_off[wv][i + s] <= rel) i += s;
-                const uint32_t vv = (uint32_t)c0 + i, to = s_thr[wv][i];
+                const uint32_t vv = (uint32_t)c0 + i, to = EXACT ? 0u : s_thr[wv][i];
                 const uint32_t mi = m & 15u, mo = m >> 4, mm = mi > mo ? mi : mo;
                 uint32_t oc = 0;
-                if constexpr (!FAULTS) {
+                if constexpr (EXACT) {  // the in side only: the sender's bound of this tick (k_fanout_kth), one gather
+                    const uint64_t bd = xa.bound[u];
+                    const bool rdown = FAULTS && s_down[FAULTS ? wv : 0u][FAULTS ? i : 0u] != 0u;
+                    for (uint32_t c = 0; c < mi; c++) {  // (a silent sender's mi is 0: the setter)
+                        const bool arrives = fanout_exact_pass(fanout_exact_draw(a.seed, u, vv, c, a.tick), bd);
+                        bool lost = false;
+                        if (loss_on) {
+                            uint32_t y[2];
+                            draw_rolling(f.loss_seed, kLossKey1, vv, u, c, a.tick, y);
+                            lost = loss_pass(u < vv ? y[0] : y[1], f.loss_thr);
+                        }
+                        if constexpr (FAULTS) {
+                            tdownc += (arrives && rdown) ? 1u : 0u;
+                            tlost += (arrives && !rdown && lost) ? 1u : 0u;
+                        }
+                        sel |= arrives && !rdown && !lost;
+                    }
+                } else if constexpr (!FAULTS) {
                     for (uint32_t c = 0; c < mm; c++) {
                         uint32_t x[2];
                         fanout_draw(a.seed, vv, u, c, a.tick, x);
@@ -235,15 +358,18 @@ __device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const Faul
         }
         __builtin_amdgcn_wave_barrier();
         if (v < a.n) {
-            const uint32_t ic = s_in[wv][lane], oc = s_out[wv][lane];
-            const uint32_t r = a.recv[v], g = a.gen[v];
-            const uint32_t d = (r - a.recv_prev[v]) + (g - a.gen_prev[v]);
-            if (d && oc) a.sent_f[v] += (unsigned long long)oc * d;
-            a.recv_prev[v] = r;
-            a.gen_prev[v] = g;
+            const uint32_t ic = s_in[wv][lane];
+            if constexpr (!EXACT) {  // (exact: k_fanout_kth owns the out side and rolls the copies)
+                const uint32_t oc = s_out[wv][lane];
+                const uint32_t r = a.recv[v], g = a.gen[v];
+                const uint32_t d = (r - a.recv_prev[v]) + (g - a.gen_prev[v]);
+                if (d && oc) a.sent_f[v] += (unsigned long long)oc * d;
+                a.recv_prev[v] = r;
+                a.gen_prev[v] = g;
+                tout += oc;
+            }
             a.cnt[v] = ic;
             tin += ic;
-            tout += oc;
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -272,9 +398,48 @@ __device__ __forceinline__ void fanout_count_body(const FanoutArgs a, const Faul
     }
 }
 
-__global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) { fanout_count_body<false>(a, FaultArgs{}); }
+__global__ __launch_bounds__(256) void k_fanout_count(FanoutArgs a) { fanout_count_body<false, false>(a, FaultArgs{}, ExactArgs{}); }
 // the count pass with faults: down rows select nothing, a lost copy selects nothing
-__global__ __launch_bounds__(256) void k_fanout_count_faults(FanoutArgs a, FaultArgs f) { fanout_count_body<true>(a, f); }
+__global__ __launch_bounds__(256) void k_fanout_count_faults(FanoutArgs a, FaultArgs f) { fanout_count_body<true, false>(a, f, ExactArgs{}); }
+// the count passes of exact-k fanout: the in side against the senders' bounds, no out side
+__global__ __launch_bounds__(256) void k_fanout_count_exact(FanoutArgs a, ExactArgs xa) { fanout_count_body<false, true>(a, FaultArgs{}, xa); }
+__global__ __launch_bounds__(256) void k_fanout_count_exact_faults(FanoutArgs a, FaultArgs f, ExactArgs xa) {
+    fanout_count_body<true, true>(a, f, xa);
+}
+
+// Exact-k fanout, the pass in front of the count pass: bound[u] = q(u, T) and the out side of every node, one
+// lane per row (the head of this file).  SLOTS: the LDS slots per lane, 8 or 32 -- the host picks the
+// smaller one that holds the largest k of a selecting node (16 KiB or 64 KiB a block).
+template <uint32_t SLOTS>
+__global__ __launch_bounds__(256) void k_fanout_kth(FanoutArgs a, ExactArgs xa) {
+    __shared__ uint64_t s_keep[SLOTS][256];
+    const uint32_t tid = threadIdx.x;
+    unsigned long long tout = 0ull;
+    for (uint64_t u = (uint64_t)blockIdx.x * 256u + tid; u < a.n; u += (uint64_t)gridDim.x * 256u) {
+        const uint32_t k = xa.kx[u];
+        uint32_t oc = xa.xout[u];
+        uint64_t bd = kFanoutExactAll;
+        if (k != 0u && k <= SLOTS) {  // (k <= SLOTS always: the host's choice; the bound on the LDS index)
+            FanoutExactTop s = {0ull, 0u, 0u, 0u};
+            for (int64_t j = a.rowptr[u], je = a.rowptr[u + 1u]; j < je; j++) {
+                const uint32_t v = (uint32_t)a.col[j], mo = (uint32_t)a.emult[j] >> 4;
+                for (uint32_t c = 0; c < mo; c++)
+                    fanout_exact_push(s, &s_keep[0][tid], 256u, k, fanout_exact_draw(a.seed, (uint32_t)u, v, c, a.tick));
+            }
+            bd = s.mx;
+            oc = s.have + s.ties;
+        }
+        xa.bound[u] = bd;
+        const uint32_t r = a.recv[u], g = a.gen[u];
+        const uint32_t d = (r - a.recv_prev[u]) + (g - a.gen_prev[u]);
+        if (d && oc) a.sent_f[u] += (unsigned long long)oc * d;
+        a.recv_prev[u] = r;
+        a.gen_prev[u] = g;
+        tout += oc;
+    }
+    for (int off = 32; off > 0; off >>= 1) tout += __shfl_xor(tout, off, 64);
+    if ((tid & 63u) == 0u && tout) atomicAdd(a.stat + (blockIdx.x & (kFanoutStatReplicas - 1u)) * kFanoutStatLine + 1, tout);
+}
 
 __global__ __launch_bounds__(256) void k_fanout_compact(FanoutArgs a) {
     const uint32_t lane = threadIdx.x & 63u;

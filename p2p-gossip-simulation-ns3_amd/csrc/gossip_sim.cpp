@@ -58,7 +58,8 @@ struct Options {
     std::string schedule = "exact";    // exact (the reference's mt19937 stream) | philox (GPU)
     std::string reach;                 // reach profile per counted event (GOSSIP_F_REACH)
     uint32_t fanout = 0;               // fanout-limited gossip: expected fanout (0: the reference's flood)
-    uint64_t fanoutSeed = 1;           // ... and the seed of its per-(link, tick) draws
+    uint32_t fanoutExact = 0;          // exact-k fanout: every sender pushes to exactly K peer copies per tick
+    uint64_t fanoutSeed = 1;           // ... and the seed of the per-(link, tick) draws of either
     std::string outages;               // fault injection: outage file, lines "node from_ns to_ns"
     double loss = 0.0;                 // ... message-loss probability per made Send
     uint64_t lossSeed = 1;             // ... and the seed of its per-(link, tick) draws
@@ -77,7 +78,7 @@ void usage() {
                  "                  [--links=F] [--events=F] [--dumpTrace=F] [--netanim=F] [--noPackets]\n"
                  "                  [--log=F|-] [--gpus=N] [--shards=S] [--layout=shards|rows]\n"
                  "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n"
-                 "                  [--fanout=K] [--fanoutSeed=S] [--uniqueIds]\n"
+                 "                  [--fanout=K | --fanoutExact=K] [--fanoutSeed=S] [--uniqueIds]\n"
                  "                  [--outages=F] [--loss=P] [--lossSeed=S]\n");
 }
 
@@ -149,6 +150,7 @@ bool parse(int argc, char** argv, Options& o) {
         else if (key == "schedule") { if (!need()) return false; o.schedule = val; }
         else if (key == "reach") { if (!need()) return false; o.reach = val; }
         else if (key == "fanout") { if (!num(d) || d < 1 || d > 4294967295.0) return false; o.fanout = (uint32_t)d; }
+        else if (key == "fanoutExact") { if (!num(d) || d < 1 || d > 4294967295.0) return false; o.fanoutExact = (uint32_t)d; }
         else if (key == "fanoutSeed" || key == "lossSeed") {
             if (!need()) return false;
             char* end = nullptr;
@@ -167,6 +169,10 @@ bool parse(int argc, char** argv, Options& o) {
             std::fprintf(stderr, "unknown option --%s\n", key.c_str());
             return false;
         }
+    }
+    if (o.fanout && o.fanoutExact) {
+        std::fprintf(stderr, "--fanout and --fanoutExact exclude each other: an expected fanout or an exact one\n");
+        return false;
     }
     return true;
 }
@@ -233,7 +239,7 @@ struct RowGroup {
 void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank, uint32_t count,
                 const uint8_t* uid, RowGroup* group, const gossip_topology* topo, const gossip_schedule* sched,
                 const std::vector<double>& per_t, bool link_timing, bool want_trace, double mem_limit_mb,
-                uint32_t fanout, uint64_t fanout_seed, const std::vector<gossip_outage>* outages, uint32_t loss_thr,
+                uint32_t fanout, bool fanout_exact, uint64_t fanout_seed, const std::vector<gossip_outage>* outages, uint32_t loss_thr,
                 uint64_t loss_seed, Part& out) {
     gossip_config cfg = base;
     cfg.device = device;
@@ -259,7 +265,9 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
     // NS-3 link timing: 5 Mbps DataRate (p2pnetwork.cc:113) = 1600 ns/byte, 54 header bytes
     // (PPP + IPv4 + TCP with timestamps), 1 ns TcpSocketBase send deferral (gossip.h)
     if (link_timing && (rc = gossip_engine_set_link_timing(eng, 1600, 54, 1))) return fail("link timing", rc);
-    if (fanout && (rc = gossip_engine_set_fanout(eng, fanout, fanout_seed))) return fail("fanout", rc);
+    if (fanout && (rc = fanout_exact ? gossip_engine_set_fanout_exact(eng, fanout, fanout_seed)
+                                     : gossip_engine_set_fanout(eng, fanout, fanout_seed)))
+        return fail("fanout", rc);
     if (outages && (rc = gossip_engine_set_outages(eng, outages->size(), outages->data()))) return fail("outages", rc);
     if (loss_thr && (rc = gossip_engine_set_link_loss(eng, loss_thr, loss_seed))) return fail("link loss", rc);
     for (double t : per_t)  // Start(): p2pnetwork.cc:201-204
@@ -445,7 +453,7 @@ int main(int argc, char** argv) {
                 // device g runs shards g, g + N, ... (rows: exactly rank g)
                 for (uint32_t r = g; r < count; r += ng)
                     run_engine(cfg, o.device + (int)g, rows, r, count, uid.data(), gp, topo, sched, per_t,
-                               o.linkTiming, want_trace, o.memLimitMB, o.fanout, o.fanoutSeed,
+                               o.linkTiming, want_trace, o.memLimitMB, o.fanoutExact ? o.fanoutExact : o.fanout, o.fanoutExact != 0, o.fanoutSeed,
                                o.outages.empty() ? nullptr : &outages, loss_thr, o.lossSeed, parts[r]);
             });
         for (auto& t : th) t.join();
@@ -462,8 +470,9 @@ int main(int argc, char** argv) {
             continue;
         }
         std::fprintf(stderr, "gossip_sim: %s\n", err.c_str());
-        if (o.fanout && !o.uniqueIds && err.find("unique share ids") != std::string::npos)
-            std::fprintf(stderr, "gossip_sim: --fanout needs unique share ids: add --uniqueIds to renumber them\n");
+        if ((o.fanout || o.fanoutExact) && !o.uniqueIds && err.find("unique share ids") != std::string::npos)
+            std::fprintf(stderr, "gossip_sim: --fanout%s needs unique share ids: add --uniqueIds to renumber them\n",
+                         o.fanoutExact ? "Exact" : "");
         return 1;
     }
     if (o.hopBatch)

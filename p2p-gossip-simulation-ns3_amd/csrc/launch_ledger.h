@@ -83,7 +83,8 @@ constexpr bool dense_split_has_empty(uint32_t nst, uint32_t ksplit) {
 struct LaunchRecord {
     uint32_t kernel;   // LaunchKernel
     uint32_t variant;  // k_pull: pull_key; k_pull_young: its bool template argument; k_dense_bits: ksplit;
-                       // k_fanout: 1 the count pass, 2 the compact pass; else 0
+                       // k_fanout: 1 / 3 / 5 / 6 the count pass (plain, faults, exact, exact with faults), 2 the compact
+                       // pass, 4 the k-th-draw pass; else 0
     uint64_t launches;
     uint64_t strided;
 };

@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_get_reach_totals", "gossip_engine_get_reach",
     "gossip_engine_set_fanout", "gossip_engine_set_forward_thresholds", "gossip_fanout_selected",
     "gossip_engine_get_fanout_counters",
+    "gossip_engine_set_fanout_exact", "gossip_engine_set_fanout_counts", "gossip_fanout_exact_row",
     "gossip_engine_set_outages", "gossip_engine_set_link_loss", "gossip_fault_lost",
     "gossip_engine_get_fault_counters", "gossip_outages_load",
 )
@@ -280,6 +281,9 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_set_forward_thresholds": (C.c_int, [P, P, u64]),
         "gossip_fanout_selected": (C.c_int, [u64, u32, u32, u32, i64, u32]),
         "gossip_engine_get_fanout_counters": (C.c_int, [P, C.POINTER(gossip_fanout_counters)]),
+        "gossip_engine_set_fanout_exact": (C.c_int, [P, u32, u64]),
+        "gossip_engine_set_fanout_counts": (C.c_int, [P, P, u64]),
+        "gossip_fanout_exact_row": (C.c_int, [u64, u32, u32, P, P, u32, i64, P, P]),
         "gossip_engine_set_outages": (C.c_int, [P, u64, P]),
         "gossip_engine_set_link_loss": (C.c_int, [P, u32, u64]),
         "gossip_fault_lost": (C.c_int, [u64, u32, u32, u32, i64, u32]),
@@ -472,6 +476,21 @@ def fanout_selected(seed: int, sender: int, receiver: int, copy: int, tick: int,
                                                       int(thr)))
 
 
+def fanout_exact_row(seed: int, sender: int, receiver, copy, k: int, tick: int, draws: bool = False):
+    """The exact-k selection rule (gossip.h, gossip_fanout_exact_row) for one sender's out-copies
+    (receiver[i], copy[i]): a bool array, the copies sent in tick `tick` under the fanout count k -- and
+    the 64-bit draws with draws=True.  No engine, no device."""
+    receiver = np.ascontiguousarray(receiver, np.uint32)
+    copy = np.ascontiguousarray(copy, np.uint32)
+    if receiver.ndim != 1 or receiver.shape != copy.shape:
+        raise GossipError("fanout_exact_row: one copy number per receiver", E_INVAL)
+    sel = np.zeros(receiver.size, np.uint8)
+    w = np.zeros(receiver.size, np.uint64) if draws else None
+    _check(load_library().gossip_fanout_exact_row(int(seed), int(sender), receiver.size, _vp(receiver), _vp(copy), int(k),
+                                                  int(tick), _vp(sel), _vp(w) if draws else None), "fanout exact row")
+    return (sel.astype(bool), w) if draws else sel.astype(bool)
+
+
 def fault_lost(seed: int, sender: int, receiver: int, copy: int, tick: int, loss_thr: int) -> bool:
     """The message-loss rule (gossip.h, gossip_fault_lost): is the Send sender -> receiver, copy `copy`,
     made in tick `tick` lost under the threshold `loss_thr`?  No engine, no device."""
@@ -655,6 +674,19 @@ class Engine:
             raise GossipError("set_forward_thresholds: one threshold per node", E_INVAL)
         _check(load_library().gossip_engine_set_forward_thresholds(self._h, _vp(thr), int(seed)),
                "set forward thresholds")
+
+    def set_fanout_exact(self, k: int, seed: int = 1):
+        """Exact-k fanout (gossip.h, gossip_engine_set_fanout_exact): every node sends to exactly k of its
+        peer copies per tick (to all of them if it has no more than k); after the graph, before the schedule."""
+        _check(load_library().gossip_engine_set_fanout_exact(self._h, int(k), int(seed)), "set fanout exact")
+
+    def set_fanout_counts(self, k, seed: int = 1):
+        """Exact-k fanout with a fanout count per node (0: a silent node; at most 32 at a node with more
+        peer copies than its count); after the graph, before the schedule."""
+        k = np.ascontiguousarray(k, np.uint32)
+        if k.size != self.n:
+            raise GossipError("set_fanout_counts: one count per node", E_INVAL)
+        _check(load_library().gossip_engine_set_fanout_counts(self._h, _vp(k), int(seed)), "set fanout counts")
 
     def fanout_counters(self) -> gossip_fanout_counters:
         c = gossip_fanout_counters()

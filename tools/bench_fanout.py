@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """bench.py's workload under fanout-limited gossip: the cost figures of DESIGN section 6.
 
-    python tools/bench_fanout.py [--fanout 2,4,8] [--fanout-seed 1] [--out FILE.json]
+    python tools/bench_fanout.py [--fanout 2,4,8] [--fanout-seed 1] [--exact] [--out FILE.json]
                                  [-- bench.py arguments, default: --gpus 1 --steps 20 --warmup 5]
 
 bench.py runs unchanged, once per fanout (a fanout of 0 in the list runs the plain flood the same way:
 the figures to compare against).  Engine.set_schedule is wrapped: it calls
-set_fanout(k, seed) first (after the graph, before the schedule, as the mode requires) and renumbers
+set_fanout(k, seed) -- with --exact, set_fanout_exact(k, seed): exactly k Sends per node and tick, with
+k_fanout_kth in the measured passes -- first (after the graph, before the schedule, as the mode requires) and renumbers
 the share ids with gossip.unique_ids -- bench.py's synthetic schedule reuses ids above 128,849 nodes,
 and fanout mode needs them unique.  Reach profiles are switched on through the environment
 (GOSSIP_REACH=1), as tools/bench_reach.py does.  Engine.counters() is wrapped to print, at each read,
@@ -32,12 +33,12 @@ import gossip  # noqa: E402
 _counters = gossip.Engine.counters
 _set_schedule = gossip.Engine.set_schedule
 _reset_timing = gossip.Engine.reset_timing
-_state = dict(k=0, seed=1, probes=[], engines=0)
+_state = dict(k=0, seed=1, exact=False, probes=[], engines=0)
 
 
 def _set_schedule_fanout(self, ev):
     if _state["k"]:  # (--fanout 0: the flood over the same renumbered schedule, for comparison)
-        self.set_fanout(_state["k"], _state["seed"])
+        (self.set_fanout_exact if _state["exact"] else self.set_fanout)(_state["k"], _state["seed"])
     _set_schedule(self, gossip.unique_ids(ev))
 
 
@@ -50,7 +51,7 @@ def _counters_probe(self):
     if self._fanout_reads == 1:
         self._fanout_engine = _state["engines"]
         _state["engines"] += 1
-    p = dict(fanout=_state["k"], engine=self._fanout_engine, read=self._fanout_reads - 1,
+    p = dict(fanout=_state["k"], exact=_state["exact"], engine=self._fanout_engine, read=self._fanout_reads - 1,
              after_reset=bool(getattr(self, "_fanout_reset", False)), ticks=c.ticks, fanout_launches=f.launches, fanout_ms=f.ms, fanout_bytes=f.bytes,
              fanout_entries=f.entries, selected_in=f.selected_in, selected_out=f.selected_out,
              fanout_ms_per_tick=f.ms / f.launches if f.launches else None,
@@ -77,6 +78,10 @@ def main():
     ks, seed, out = [2, 4, 8], 1, None
     i = 0
     while i < len(argv):
+        if argv[i] == "--exact":
+            _state["exact"] = True
+            i += 1
+            continue
         if argv[i] == "--fanout":
             ks = [int(x) for x in argv[i + 1].split(",")]
         elif argv[i] == "--fanout-seed":
@@ -103,7 +108,7 @@ def main():
         last = {}
         for p in _state["probes"]:
             last[(p["engine"], p["after_reset"])] = p
-        runs.append(dict(fanout=k, seed=seed, timed=[p for (e, a), p in sorted(last.items()) if a],
+        runs.append(dict(fanout=k, seed=seed, exact=_state["exact"], timed=[p for (e, a), p in sorted(last.items()) if a],
                          ramp=[p for (e, a), p in sorted(last.items()) if not a]))
     if out:
         with open(out, "w") as f:
