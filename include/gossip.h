@@ -389,10 +389,12 @@ int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* 
  *   - A Send u -> v made in tick T is delivered only if v is up in tick T + 1.  The Send is still made:
  *     it is counted in sent[u] and edge_events (the sender does not know).  It delivers nothing: no recv,
  *     no trace record, no reach count.
- *   - There is no sender test: a node forwards in the tick in which it first received, so a sender is up.
+ *   - Without gossip_engine_set_rounds there is no sender test: a node forwards in the tick in which it
+ *     first received, so a sender is up.  With r > 1 rounds a later round can fall into an outage of the
+ *     sender: see SENDER OUTAGES below (multi-round push).
  *   - A node that comes back up keeps its seen set.  It has missed what arrived while it was down and
  *     gets such a share later only if some peer first-receives it later: crash-recover without state loss
- *     and without retransmission.
+ *     and without retransmission (gossip_engine_set_rounds adds the re-sends of a multi-round push).
  *   MESSAGE LOSS.  A Send u -> v, copy c, made in tick T is lost iff
  *     lo = min(u, v), hi = max(u, v)
  *     y  = Philox4x32-10(counter = (lo, hi, (uint32)T, c),
@@ -452,6 +454,55 @@ int gossip_outages_load(uint32_t num_nodes, int64_t latency_ns, const char* path
                         gossip_outage* out, uint64_t* count, uint64_t* skipped);
 /* The first four since the last gossip_engine_reset_timing; all zero on an engine without faults. */
 int gossip_engine_get_fault_counters(gossip_engine* e, gossip_fault_counters* c);
+
+/* Multi-round push: a node keeps pushing a new share for r ticks (the "rounds" of lpbcast and of the
+ * rumour-mongering analyses: fanout x rounds).  Time is in ticks as in fanout mode.
+ *   THE RULE.  A node u that first contacts a share in tick T -- by its own generation or by a first
+ * reception -- makes Sends of that share in the ticks T, T + 1, ..., T + r - 1.  Each of those ticks uses that
+ * tick's selection for (u, v, c, tick): the binomial fanout draw, the exact-k subset, the loss draw and the
+ * receiver's outage test for tick + 1.  The draws belong to (sender, receiver, copy, tick), so a re-send gets a
+ * fresh peer selection and a fresh loss draw.  A receiver that has seen the share drops a re-send like any
+ * duplicate.
+ *   A share's column is ALIVE in tick X iff g + (X - floor(g / L)) * L < t_cut, g its generation time: the
+ * condition under which a first arrival in X is counted.  Sends of a dead column are not made.
+ *   r = 1 is the engine without this call, bit for bit.
+ *   SENDER OUTAGES.  With r > 1 a sender can be down.  A node that is down in tick X makes no Sends in X and
+ * none is counted; its remaining rounds still elapse: the last Send tick of a contact made in T is T + r - 1
+ * whether or not the node was up.  A down node has no first contacts (deliveries to it and its generations
+ * are dropped, as before).
+ *   COUNTERS.  sent[u] and edge_events count every Send made, re-sends included: out-count(u, X) x the number
+ * of shares in u's send set in X.  recv, fwd (one per first reception), processed, gen, the snapshots, the
+ * trace and the reach profiles keep their meaning ("hop" is ticks since the generation); a re-send never
+ * creates a trace record or a reach count.
+ *   LIVENESS.  A column stays live while any node still has a round of it pending, a node that is down in
+ * the tick included (its rounds elapse, but until they have the column could still be sent): the window holds
+ * a share's word up to r - 1 ticks longer than a flood does (words_hw, and the capacity a run needs, grow
+ * with r), and a word is reused only when no node has a re-send pending in it.  gossip_engine_end_tick is
+ * the cut's and does not move.
+ *   DETERMINISM.  The result is a pure function of (graph, events, latency, cut, r, fanout inputs and seed,
+ * fault inputs and seed): no tuning option, tile layout or share sharding changes it, and share shards add
+ * up to the single engine.
+ *   gossip_engine_set_rounds: 1 <= r <= 16 (GOSSIP_EINVAL otherwise); after the graph and before the
+ * schedule (GOSSIP_ESTATE otherwise), in any order with the fanout and fault setters -- none discards what
+ * another set.  On an engine with no thinning yet, r > 1 turns the thinning path on with every threshold
+ * 0xffffffff, as the fault setters do, and refuses what they refuse with the same messages; option
+ * dense_rows resolves to off and forcing it on is GOSSIP_EINVAL.  set_rounds(1) after set_rounds(3) switches
+ * the feature off again and frees its buffers; set_rounds(1) on an engine that never had r > 1 does nothing
+ * (it does not turn thinning on).  Per-node arrays are allocated by the call, the counter planes
+ * (bit_length(r - 1) <= 4 buffers of the frontier's shape, csrc/rounds_kernel.h) with the window at
+ * gossip_engine_set_schedule; both are in device_bytes and under mem_limit. */
+int gossip_engine_set_rounds(gossip_engine* e, uint32_t r);
+typedef struct gossip_rounds_counters {
+    uint64_t launches;     /* k_rounds launches (ticks with a live window)                               */
+    uint64_t resent_bits;  /* (node, share) Send-set members that were re-sends, summed over ticks        */
+    uint64_t rows_visited; /* (node, tile) rows that had new bits or pending counters, summed over ticks  */
+    double ms;             /* summed HIP-event time of the launches (GOSSIP_F_TIMING)                     */
+    uint64_t bytes;        /* bytes they moved, counted by the kernel: 16 B of gate words per node and 64
+                              tiles, and per visited word 8 B of keep mask, 8 B per frontier or plane word
+                              read and per word written                                                  */
+} gossip_rounds_counters;
+/* Since the last gossip_engine_reset_timing; all zero on an engine without rounds (r = 1). */
+int gossip_engine_get_rounds_counters(gossip_engine* e, gossip_rounds_counters* c);
 /* Tuning options of one engine (results never depend on them; A/B runs and tests).  The
  * environment variable in brackets gives the default:
  *   "pull_nt"          -1 auto (non-temporal rows when the live frontier n x wact x 8 B exceeds
@@ -539,6 +590,9 @@ int gossip_engine_get_fault_counters(gossip_engine* e, gossip_fault_counters* c)
  *   "fanout_grid"      fanout mode: blocks of the two k_fanout passes, 0 = auto (one wave per 64 nodes,
  *                      at most 64 blocks per compute unit); small values make a wave loop over
  *                      several 64-node chunks (tests)                      [GOSSIP_FANOUT_GRID]
+ *   "rounds_grid"      multi-round push: blocks of k_rounds, 0 = auto (one block per 16 rows, at most 32
+ *                      per compute unit); small values make a block loop over several row groups
+ *                      (tests)                                             [GOSSIP_ROUNDS_GRID]
  *   "xchunks"          row partition: row chunks per tick of the pipelined exchange, 1..16 (4);
  *                      equal on every rank of a partition                    [GOSSIP_XCHUNKS]
  *   "rehearse_rows"    diagnostic, R >= 2 on an unpartitioned CSR engine (before the schedule;
@@ -681,6 +735,8 @@ int gossip_engine_reset_timing(gossip_engine* e);
  *             of 1 on an engine with outages or loss; strided: a wave looped over several 64-node chunks),
  *             exact-k: 4 the k-th-draw pass (k_fanout_kth), 5 the exact count pass, 6 the exact count pass
  *             with faults (5 / 6 in place of 1 / 3; the compact pass is 2 in every mode);
+ *             GOSSIP_K_ROUNDS: the number of counter planes, bit_length(r - 1) (strided: a block looped
+ *             over several groups of 16 rows);
  *             0 otherwise
  *   launches  launches of that variant
  *   strided   of those, launches whose grid had fewer waves than work units, so that a wave's
@@ -696,6 +752,7 @@ int gossip_engine_reset_timing(gossip_engine* e);
 #define GOSSIP_K_DENSE_DEDUP 4
 #define GOSSIP_K_REACH 5      /* k_reach / k_reach_slots (GOSSIP_F_REACH only) */
 #define GOSSIP_K_FANOUT 6     /* k_fanout_count / k_fanout_compact (fanout mode only) */
+#define GOSSIP_K_ROUNDS 7     /* k_rounds (gossip_engine_set_rounds, r > 1 only) */
 #define GOSSIP_PULL_NT 1u     /* non-temporal row accesses                  */
 #define GOSSIP_PULL_SP 2u     /* tile masks, saturation bits (32 x 1 lanes) */
 #define GOSSIP_PULL_PUSH 4u   /* push marks                                 */

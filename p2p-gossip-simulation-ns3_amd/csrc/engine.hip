@@ -52,6 +52,7 @@
 #include "launch_ledger.h"
 #include "reach_kernel.h"
 #include "fanout_kernel.h"
+#include "rounds_kernel.h"
 
 using gossip::set_error;
 using gossip::PullShape;
@@ -1077,6 +1078,30 @@ struct gossip_engine {
         return !h_out_from.empty() && t >= 0 && gossip::outage_down(h_out_off.data(), h_out_from.data(), h_out_to.data(), v, (uint64_t)t);
     }
     int outages_setup(uint64_t count, const gossip_outage* o);
+    // ---- multi-round push (gossip_engine_set_rounds; rounds_kernel.h): k_rounds between the reach pass and
+    // the fanout passes turns the tick's new bits into the send sets and keeps the remaining rounds in bit
+    // planes.  The per-node arrays are the setter's; the planes and their occupancy words have the window's
+    // shape, which the schedule fixes, so alloc_device makes them and grow widens them.
+    uint32_t rounds = 1;               // r; 1: off, nothing allocated, nothing launched
+    uint32_t rounds_np = 0;            // planes: bit_length(r - 1)
+    uint64_t* d_rplane[gossip::kRoundsMaxPlanes] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned long long* d_pnz = nullptr;             // n x ntw: some plane word of the node's tile row is non-zero
+    uint32_t *d_send_cum = nullptr, *d_send_prev = nullptr;  // n + 1: FanoutArgs::recv / recv_prev in rounds mode
+    uint32_t *d_rzero[2] = {nullptr, nullptr};       // n + 1 zeros: FanoutArgs::gen / gen_prev in rounds mode
+    unsigned long long* d_rstat = nullptr;           // kRoundsStats words
+    uint64_t rounds_bytes = 0;         // device bytes of the per-node arrays (in device_bytes)
+    uint64_t rounds_plane_bytes = 0;   // device bytes of the planes and d_pnz (in device_bytes)
+    int64_t opt_rounds_grid = 0;       // blocks of k_rounds, 0 = auto
+    uint64_t rounds_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_rounds;
+    double rounds_ms_done = 0.0;
+    int rounds_setup(uint32_t r);      // the setter: per-node arrays (r > 1) or rounds_free (r = 1)
+    int rounds_alloc_planes();         // alloc_device: the planes at the window's stride
+    int rounds_launch(int64_t t);      // tick_step_b: after reach_launch, before fanout_launch
+    void rounds_free();
+    uint64_t rounds_plane_need(uint32_t words) const {
+        return rounds > 1 ? (uint64_t)rounds_np * n * words * 8 + (uint64_t)n * ((words + 1023u) / 1024u) * 8 : 0ull;
+    }
 
     ~gossip_engine();
     int alloc_device();
@@ -1222,6 +1247,11 @@ gossip_engine::~gossip_engine() {
     fanout_free();
     hipFree(d_xk); hipFree(d_xout); hipFree(d_xbound);
     hipFree(d_out_off); hipFree(d_out_from); hipFree(d_out_to);
+    for (auto& p : timers_rounds) {
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    rounds_free();
     if (comm && !aborted.load()) ncclCommDestroy(comm);  // (an aborted communicator is already freed)
     for (int k = 0; k < kRing; k++) {
         hipFree(d_ctl[k]); hipFree(d_births[k]); hipFree(d_gphase[k]); hipFree(d_wflags[k]);
@@ -1503,7 +1533,10 @@ int gossip_engine::alloc_device() {
             ecc = std::max(0, graph_derived(false, true, false).ecc);
         }
         // (the window widens itself if this is short: gossip_engine::grow)
-        const int64_t life = ecc + kLag + 1;
+        // (multi-round push: a column stays live r - 1 ticks past its last first contact; a flood that loss
+        //  or outages stretch further -- up to r - 1 extra ticks per hop -- widens the window like any other
+        //  short estimate)
+        const int64_t life = ecc + kLag + 1 + (int64_t)(rounds - 1);
         const int64_t nt = tick_end - tick0;
         uint64_t peak = 0, run = 0;
         std::vector<uint64_t> cnt((size_t)nt, 0);
@@ -1561,7 +1594,8 @@ int gossip_engine::alloc_device() {
         const uint64_t other = (uint64_t)n * 24 + nnz * 4 + ((uint64_t)n + 1) * 8 + slot_bytes +
                                24ull * n * ((want + 1023u) / 1024u) + (4ull << 30);  // + RCCL / context (24: nz x 2 + sat)
         const uint64_t per_word = 3ull * n * 8 + (dense ? 16ull * n_pad : 0ull) +  // (DENSE: FT x 2)
-                                  (reach ? (uint64_t)kRing * 257u : 0ull);         // (reach: the count ring)
+                                  (reach ? (uint64_t)kRing * 257u : 0ull) +        // (reach: the count ring)
+                                  (uint64_t)(rounds > 1 ? rounds_np : 0u) * n * 8;  // (rounds: the counter planes)
         uint64_t fit = freeb > other ? ((uint64_t)freeb - other) / per_word : 0ull;
         fit = fit / kTileWords * kTileWords;
         stride = (uint32_t)std::max<uint64_t>(stride, std::min<uint64_t>(want / kTileWords * kTileWords, fit));
@@ -1581,7 +1615,7 @@ int gossip_engine::alloc_device() {
     const uint64_t bm_seen = (uint64_t)seen_n * stride * 8;
     const uint64_t need = 2 * bm + bm_seen + (uint64_t)n * 24 + (nnz * 4) + ((uint64_t)n + 1) * 8 + slot_bytes +
                           24ull * n * ((stride + 1023u) / 1024u) +
-                          (dense ? (uint64_t)stride * 8 * n_pad : 0ull) + reach_ring_bytes(stride);
+                          (dense ? (uint64_t)stride * 8 * n_pad : 0ull) + reach_ring_bytes(stride) + rounds_plane_need(stride);
     if (need > (uint64_t)freeb)
         return set_error(GOSSIP_ENOMEM, "device memory: need " + std::to_string(need) +
                                             " bytes for a " + std::to_string(stride) +
@@ -1638,6 +1672,8 @@ int gossip_engine::alloc_device() {
         HIP_TRY(hipMalloc(&d_live[k], (size_t)stride * 8));
         HIP_TRY(hipMemsetAsync(d_live[k], 0, (size_t)stride * 8, stream));
     }
+    if (rounds > 1)  // (its bytes are in `need` above)
+        if (int rc = rounds_alloc_planes()) return rc;
     const size_t nsc = 2 + 2 * snaps.size();
     HIP_TRY(hipMalloc(&d_scalars, nsc * 8));
     HIP_TRY(hipMemsetAsync(d_scalars, 0, nsc * 8, stream));
@@ -1689,6 +1725,7 @@ int gossip_engine::alloc_device() {
     device_bytes = 2 * bm + bm_seen + (d_sat ? 24ull : 16ull) * n * ntw + (uint64_t)n * 20 + nnz * 4 + ((uint64_t)n + 1) * 8 + 2ull * stride * 8 + slot_bytes +
                    kRing * ((uint64_t)stride * sizeof(WordCtl) + (uint64_t)bcap * sizeof(Birth) + pcap * 4);
     device_bytes += fanout_bytes + outage_bytes + exact_bytes;  // (allocated by the fanout / fault setters; 0 without one)
+    device_bytes += rounds_bytes + rounds_plane_bytes;          // (set_rounds' arrays and, above, its planes; 0 at r = 1)
     if (dense) {
         const uint64_t ft = (uint64_t)stride * 8 * n_pad;
         snz_nstw = (n_pad / kStageK + 63u) / 64u;
@@ -1748,8 +1785,13 @@ int gossip_engine::grow(uint32_t new_stride) {
     size_t freeb = 0, totalb = 0;
     HIP_TRY(hipMemGetInfo(&freeb, &totalb));
     int ok = nb + (64ull << 20) <= (uint64_t)freeb ? 1 : 0;
+    // Rounds mode widens 3 + P buffers one after another: beside the new bitmap at the peak there must be room
+    // for what each of the others adds, or a later hipMalloc fails where GOSSIP_ECAPACITY is the answer (a
+    // caller that shards on ECAPACITY could not go on).  Engines without rounds keep the test they had.
+    if (rounds > 1 && nb + (2ull + rounds_np) * (nb - (uint64_t)n * stride * 8) + (64ull << 20) > (uint64_t)freeb) ok = 0;
     if (opt_mem_limit > 0 && device_bytes + 3 * (nb - (uint64_t)n * stride * 8) + reach_ring_bytes(new_stride) -
-                                     reach_ring_bytes(stride) > (uint64_t)opt_mem_limit)
+                                     reach_ring_bytes(stride) + rounds_plane_need(new_stride) - rounds_plane_need(stride) >
+                                 (uint64_t)opt_mem_limit)
         ok = 0;
     if (comm) {
         // Row-partitioned ranks widen in lockstep (their strides must agree for the exchange):
@@ -1770,7 +1812,10 @@ int gossip_engine::grow(uint32_t new_stride) {
         return set_error(GOSSIP_ECAPACITY, "live-share window exceeded " + std::to_string(stride) +
                                                " words per node and there is no device memory to widen it" +
                                                (comm ? " (on some rank of the row partition)" : ""));
-    uint64_t** bufs[3] = {&d_F[0], &d_F[1], &d_seen_mem};
+    // (rounds: the counter planes are rows of the same stride and move with the frontier)
+    std::vector<uint64_t**> bufs = {&d_F[0], &d_F[1], &d_seen_mem};
+    for (uint32_t k = 0; k < gossip::kRoundsMaxPlanes; k++)
+        if (d_rplane[k]) bufs.push_back(&d_rplane[k]);
     for (uint64_t** b : bufs) {
         const uint64_t rows = *b == d_seen_mem ? seen_n : n;
         uint64_t* nbuf = nullptr;
@@ -1828,6 +1873,16 @@ int gossip_engine::grow(uint32_t new_stride) {
             HIP_TRY(hipFree(d_sat));
             d_sat = q;
             device_bytes += 8ull * n * (new_ntw - ntw);
+        }
+        if (d_pnz) {  // the planes' occupancy words: widened like the nz rows
+            unsigned long long* q = nullptr;
+            HIP_TRY(hipMalloc(&q, (size_t)n * new_ntw * 8));
+            HIP_TRY(hipMemsetAsync(q, 0, (size_t)n * new_ntw * 8, stream));
+            HIP_TRY(hipMemcpy2DAsync(q, (size_t)new_ntw * 8, d_pnz, (size_t)ntw * 8, (size_t)ntw * 8, n,
+                                     hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipFree(d_pnz));
+            d_pnz = q;
         }
         ntw = new_ntw;
     }
@@ -1901,6 +1956,8 @@ int gossip_engine::grow(uint32_t new_stride) {
     col_phase.resize((size_t)new_stride * 64, 0);
     col_src.resize((size_t)new_stride * 64, UINT32_MAX);
     device_bytes += (2ull * n + seen_n) * (uint64_t)(new_stride - stride) * 8;
+    device_bytes += rounds_plane_need(new_stride) - rounds_plane_bytes;
+    rounds_plane_bytes = rounds_plane_need(new_stride);
     stride = new_stride;
     grows++;
     if (reach) return reach_alloc();  // the count ring follows the window (pending ticks folded first)
@@ -2367,7 +2424,9 @@ int gossip_engine::build_tile_lists(TickPlan& p) {
     p.use_ptile = opt_pull_tiles && !dense && !(cfg.flags & GOSSIP_F_NOSKIP) && hw;
     pt_used = p.use_ptile;
     p.sat_used = p.use_ptile && opt_pull_sat != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP) && d_sat;
-    p.dr_used = p.use_ptile && opt_dense_rows != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP);
+    // (rounds mode: off -- k_rounds finds the tick's new bits behind occupancy bits, and a send set is not the
+    //  layer model's frontier)
+    p.dr_used = p.use_ptile && opt_dense_rows != 0 && row_count == 1 && !(cfg.flags & GOSSIP_F_NOSKIP) && rounds <= 1;
     if (p.use_ptile) {
         const uint64_t need = (uint64_t)hw / kTileWords + 16ull * ((hw + kPullLdsWords - 1) / kPullLdsWords) + 16;
         if (need > ptile_cap) {
@@ -3467,6 +3526,10 @@ int gossip_engine::tick_step_b(int64_t t) {
         int rc = reach_launch(t);
         if (rc) return rc;
     }
+    if (rounds > 1) {  // new bits -> send sets, after reach has counted the new bits and before the Sends are counted
+        int rc = rounds_launch(t);
+        if (rc) return rc;
+    }
     if (fanout) {  // the tick's selected Sends: sent counts now, the thinned peer lists for the pull of t + 1
         int rc = fanout_launch(t);
         if (rc) return rc;
@@ -3843,6 +3906,9 @@ int gossip_engine::fanout_launch(int64_t t) {
     a.recv = d_recv; a.gen = d_gen; a.recv_prev = d_recv_prev; a.gen_prev = d_gen_prev; a.sent_f = d_sent_f;
     a.bitmap = d_fbitmap; a.cnt = d_fcnt; a.rowptr_t = d_rowptr_t; a.col_t = d_col_t; a.stat = d_fstat;
     a.seed = fanout_seed; a.tick = (uint32_t)t; a.n = n;
+    if (rounds > 1) {  // a node's Sends of the tick: out-count x its send set (k_rounds' cumulative sizes), re-sends included
+        a.recv = d_send_cum; a.recv_prev = d_send_prev; a.gen = d_rzero[0]; a.gen_prev = d_rzero[1];
+    }
     const uint64_t nch = ((uint64_t)n + 63) / 64;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(
         1, opt_fanout_grid > 0 ? (uint64_t)opt_fanout_grid : std::min<uint64_t>((nch + 3) / 4, 64ull * (uint64_t)num_cus));
@@ -3901,6 +3967,112 @@ int gossip_engine::fanout_launch(int64_t t) {
     return GOSSIP_OK;
 }
 
+// ---- multi-round push (rounds_kernel.h) ----------------------------------------------------
+void gossip_engine::rounds_free() {
+    for (uint32_t k = 0; k < gossip::kRoundsMaxPlanes; k++) {
+        hipFree(d_rplane[k]);
+        d_rplane[k] = nullptr;
+    }
+    hipFree(d_pnz); hipFree(d_send_cum); hipFree(d_send_prev); hipFree(d_rzero[0]); hipFree(d_rzero[1]); hipFree(d_rstat);
+    d_pnz = nullptr;
+    d_send_cum = d_send_prev = d_rzero[0] = d_rzero[1] = nullptr;
+    d_rstat = nullptr;
+}
+
+// The setter's part: r > 1 allocates the per-node arrays (once) and zeroes them; r = 1 frees them.  The
+// planes follow at the schedule (alloc_device), where the window's stride is known.
+int gossip_engine::rounds_setup(uint32_t r) {
+    HIP_TRY(hipSetDevice(device));
+    if (r == 1) {
+        rounds_free();
+        device_bytes -= rounds_bytes;
+        rounds_bytes = 0;
+        rounds = 1;
+        rounds_np = 0;
+        return GOSSIP_OK;
+    }
+    const size_t n1 = (size_t)n + 1;
+    if (!d_send_cum) {
+        const uint64_t bytes = n1 * 16 + gossip::kRoundsStats * 8;
+        if (opt_mem_limit > 0 && device_bytes + bytes > (uint64_t)opt_mem_limit)
+            return set_error(GOSSIP_ENOMEM, "rounds: the per-node arrays (" + std::to_string(bytes) + " bytes) exceed mem_limit");
+        if (hipMalloc(&d_send_cum, n1 * 4) != hipSuccess || hipMalloc(&d_send_prev, n1 * 4) != hipSuccess ||
+            hipMalloc(&d_rzero[0], n1 * 4) != hipSuccess || hipMalloc(&d_rzero[1], n1 * 4) != hipSuccess ||
+            hipMalloc(&d_rstat, gossip::kRoundsStats * 8) != hipSuccess) {
+            rounds_free();
+            (void)hipGetLastError();
+            return set_error(GOSSIP_ENOMEM, "rounds: device allocation failed");
+        }
+        rounds_bytes = bytes;
+        device_bytes += rounds_bytes;
+    }
+    HIP_TRY(hipMemsetAsync(d_send_cum, 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_send_prev, 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_rzero[0], 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_rzero[1], 0, n1 * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_rstat, 0, gossip::kRoundsStats * 8, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    rounds = r;
+    rounds_np = gossip::rounds_planes(r);
+    return GOSSIP_OK;
+}
+
+int gossip_engine::rounds_alloc_planes() {
+    const uint64_t bm = std::max<uint64_t>((uint64_t)n * stride * 8, 8), nzb = std::max<uint64_t>((uint64_t)n * ntw * 8, 8);
+    for (uint32_t k = 0; k < rounds_np; k++) {
+        HIP_TRY(hipMalloc(&d_rplane[k], bm));
+        HIP_TRY(hipMemsetAsync(d_rplane[k], 0, bm, stream));
+    }
+    HIP_TRY(hipMalloc(&d_pnz, nzb));
+    HIP_TRY(hipMemsetAsync(d_pnz, 0, nzb, stream));
+    rounds_plane_bytes = rounds_plane_need(stride);
+    return GOSSIP_OK;
+}
+
+// Tick t, after its births, exchange and reach pass, before the fanout passes and the flip: d_F[nxt] holds
+// the tick's new bits behind d_nz[nxt] and leaves holding the send sets; d_live[t % 3] takes the send sets
+// and the pending counters before its read-back.
+int gossip_engine::rounds_launch(int64_t t) {
+    if (!hw || v1 <= v0) return GOSSIP_OK;
+    const int nxt = fcur ^ 1, slot = (int)(t % kRing);
+    gossip::RoundsArgs a;
+    a.F = d_F[nxt]; a.nz = d_nz[nxt]; a.pnz = d_pnz;
+    for (uint32_t k = 0; k < gossip::kRoundsMaxPlanes; k++) a.plane[k] = d_rplane[k];
+    static_assert(sizeof(WordCtl) % 8 == 0 && offsetof(WordCtl, keep) == 8, "k_rounds reads WordCtl::keep as the second u64 of a record");
+    a.keep = reinterpret_cast<const uint64_t*>(d_ctl[slot]) + 1;
+    a.keep_stride = (uint32_t)(sizeof(WordCtl) / 8);
+    a.live = d_live[t % 3]; a.send_cum = d_send_cum;
+    const bool outs = !h_out_from.empty();
+    a.out_off = outs ? d_out_off : nullptr; a.out_from = d_out_from; a.out_to = d_out_to;
+    a.stat = d_rstat;
+    a.stride = stride; a.ntw = ntw; a.hw = hw; a.v0 = v0; a.v1 = v1;
+    a.r = rounds; a.np = rounds_np; a.tick = (uint32_t)t;
+    const uint64_t ngrp = ((uint64_t)(v1 - v0) + 15) / 16;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(
+        1, opt_rounds_grid > 0 ? (uint64_t)opt_rounds_grid : std::min<uint64_t>(ngrp, 32ull * (uint64_t)num_cus));
+    const bool strided = gossip::launch_strides(grid, ngrp);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (cfg.flags & GOSSIP_F_TIMING) {
+        e0 = get_event();
+        e1 = get_event();
+        HIP_TRY(hipEventRecord(e0, stream));
+    }
+    switch (rounds_np) {
+        case 1: gossip::k_rounds<1><<<grid, 256, 0, stream>>>(a); break;
+        case 2: gossip::k_rounds<2><<<grid, 256, 0, stream>>>(a); break;
+        case 3: gossip::k_rounds<3><<<grid, 256, 0, stream>>>(a); break;
+        default: gossip::k_rounds<4><<<grid, 256, 0, stream>>>(a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    ledger.add(gossip::LK_ROUNDS, rounds_np, strided);
+    if (e0) {
+        HIP_TRY(hipEventRecord(e1, stream));
+        timers_rounds.emplace_back(e0, e1);
+    }
+    rounds_launches++;
+    return GOSSIP_OK;
+}
+
 int gossip_engine::decode_trace(int64_t t) {
     HIP_TRY(hipStreamSynchronize(stream));
     if (hw == 0) return GOSSIP_OK;
@@ -3946,11 +4118,22 @@ int gossip_engine::decode_trace(int64_t t) {
         Sp.resize((size_t)seen_n * stride);
         HIP_TRY(hipMemcpy(Sp.data(), d_seen_mem, Sp.size() * 8, hipMemcpyDeviceToHost));
     }
+    // multi-round push: d_F[fcur] holds send sets.  A bit is a first contact of this tick iff its counter is
+    // r - 1 after k_rounds' update (a re-sent bit has at most r - 2)
+    std::vector<uint64_t> RP[gossip::kRoundsMaxPlanes];
+    for (uint32_t k = 0; rounds > 1 && k < rounds_np; k++) {
+        RP[k].resize((size_t)n * stride);
+        HIP_TRY(hipMemcpy(RP[k].data(), d_rplane[k], RP[k].size() * 8, hipMemcpyDeviceToHost));
+    }
     for (uint32_t v = v0; v < v1; v++)
         for (uint32_t w = 0; w < hw; w++) {
             const uint32_t tl = w >> 4;
             if (!nz.empty() && !ws_tile[tl] && !((nz[(size_t)v * ntw + (tl >> 6)] >> (tl & 63u)) & 1ull)) continue;  // stale row
             uint64_t x = F[(size_t)v * stride + w];
+            for (uint32_t k = 0; rounds > 1 && k < rounds_np; k++) {
+                const uint64_t pk = RP[k][(size_t)v * stride + w];
+                x &= (((rounds - 1u) >> k) & 1u) ? pk : ~pk;
+            }
             if (tl < tr_foldw.size() && tr_foldw[tl])
                 x &= ~(tr_seenf[tl] ? Fp[(size_t)v * stride + w] : Sp[(size_t)(v - seen_lo) * stride + w]);
             while (x) {
@@ -4037,6 +4220,7 @@ int gossip_engine_create(const gossip_config* cfg, gossip_engine** out) {
         e->opt_reach_hops = std::max<int64_t>(2, std::min<int64_t>(1024, env_option("GOSSIP_REACH_HOPS", 32)));
         e->opt_reach_shares = env_option("GOSSIP_REACH_SHARES", 1) != 0 ? 1 : 0;
         e->opt_fanout_grid = std::max<int64_t>(0, std::min<int64_t>(1ll << 24, env_option("GOSSIP_FANOUT_GRID", 0)));
+        e->opt_rounds_grid = std::max<int64_t>(0, std::min<int64_t>(1ll << 24, env_option("GOSSIP_ROUNDS_GRID", 0)));
         e->opt_reach_flush = std::max<int64_t>(1, std::min<int64_t>(gossip::kReachCap, env_option("GOSSIP_REACH_FLUSH", gossip::kReachCap)));
         // (GOSSIP_REACH=1 in the environment sets the flag for engines created without it: profiling
         //  an unchanged driver, tools/bench_reach.py)
@@ -4428,6 +4612,8 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
         e->opt_seen_fold = value;
     } else if (k == "dense_rows") {
         if (value < -1 || value > 1) return set_error(GOSSIP_EINVAL, "dense_rows: -1 (auto), 0 or 1");
+        if (value == 1 && e->rounds > 1)
+            return set_error(GOSSIP_EINVAL, "dense_rows: off in rounds mode (k_rounds finds the tick's new bits behind occupancy bits)");
         e->opt_dense_rows = value;
     } else if (k == "pull_gate") {
         if (value < 0 || value > 1) return set_error(GOSSIP_EINVAL, "pull_gate: 0 or 1");
@@ -4496,6 +4682,9 @@ int gossip_engine_set_option(gossip_engine* e, const char* name, int64_t value) 
     } else if (k == "fanout_grid") {
         if (value < 0 || value > (1ll << 24)) return set_error(GOSSIP_EINVAL, "fanout_grid: 0 (auto) .. 2^24 blocks");
         e->opt_fanout_grid = value;
+    } else if (k == "rounds_grid") {
+        if (value < 0 || value > (1ll << 24)) return set_error(GOSSIP_EINVAL, "rounds_grid: 0 (auto) .. 2^24 blocks");
+        e->opt_rounds_grid = value;
     } else if (k == "reach_flush") {
         if (value < 1 || value > (int64_t)gossip::kReachCap) return set_error(GOSSIP_EINVAL, "reach_flush: 1 .. 255 rows");
         e->opt_reach_flush = value;
@@ -4521,7 +4710,7 @@ int gossip_engine_get_option(const gossip_engine* e, const char* name, int64_t* 
         {"peer_order", e->opt_peer_order}, {"pull_batch", e->opt_pull_batch},
         {"seen_fold", e->opt_seen_fold}, {"reach_hops", e->opt_reach_hops},
         {"reach_shares", e->opt_reach_shares}, {"reach_flush", e->opt_reach_flush},
-        {"fanout_grid", e->opt_fanout_grid}};
+        {"fanout_grid", e->opt_fanout_grid}, {"rounds_grid", e->opt_rounds_grid}};
     for (const auto& o : opts)
         if (k == o.first) {
             *value = o.second;
@@ -4837,6 +5026,45 @@ int gossip_engine_get_fault_counters(gossip_engine* e, gossip_fault_counters* c)
         c->down_node_ticks += st[(size_t)r * gossip::kFanoutStatLine + 4];
     }
     c->launches = e->fault_launches;
+    return GOSSIP_OK;
+}
+
+// ---- multi-round push: stands where the fanout and fault setters stand; r > 1 turns the thinning path on
+// like a fault setter, r = 1 switches the feature off again (and is a no-op where it never was on)
+int gossip_engine_set_rounds(gossip_engine* e, uint32_t r) {
+    if (int rc = fanout_check(e)) return rc;
+    if (r < 1 || r > gossip::kRoundsMax) return set_error(GOSSIP_EINVAL, "rounds: 1 .. " + std::to_string(gossip::kRoundsMax));
+    if (r == 1 && e->rounds == 1) return GOSSIP_OK;
+    if (r > 1 && e->opt_dense_rows == 1)
+        return set_error(GOSSIP_EINVAL, "rounds: option dense_rows cannot be forced on (k_rounds finds the tick's new bits behind occupancy bits)");
+    if (r > 1)
+        if (int rc = thinning_on(e)) return rc;
+    return e->rounds_setup(r);
+}
+
+int gossip_engine_get_rounds_counters(gossip_engine* e, gossip_rounds_counters* c) {
+    if (!e || !c) return set_error(GOSSIP_EINVAL, "NULL argument");
+    std::memset(c, 0, sizeof(*c));
+    if (e->rounds <= 1 || !e->d_rstat) return GOSSIP_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    unsigned long long st[gossip::kRoundsStats];
+    HIP_TRY(hipMemcpy(st, e->d_rstat, sizeof(st), hipMemcpyDeviceToHost));
+    double ms = e->rounds_ms_done;
+    for (auto& p : e->timers_rounds) {
+        float x = 0.f;
+        HIP_TRY(hipEventElapsedTime(&x, p.first, p.second));
+        ms += x;
+        e->event_pool.push_back(p.first);
+        e->event_pool.push_back(p.second);
+    }
+    e->timers_rounds.clear();
+    e->rounds_ms_done = ms;
+    c->launches = e->rounds_launches;
+    c->resent_bits = st[0];
+    c->rows_visited = st[1];
+    c->ms = ms;
+    c->bytes = st[2];
     return GOSSIP_OK;
 }
 
@@ -5393,6 +5621,14 @@ int gossip_engine_reset_timing(gossip_engine* e) {
     e->fanout_ms_done = 0.0;
     e->fanout_launches = 0;
     e->fault_launches = 0;
+    for (auto& p : e->timers_rounds) {
+        e->event_pool.push_back(p.first);
+        e->event_pool.push_back(p.second);
+    }
+    e->timers_rounds.clear();
+    e->rounds_ms_done = 0.0;
+    e->rounds_launches = 0;
+    if (e->d_rstat) HIP_TRY(hipMemsetAsync(e->d_rstat, 0, gossip::kRoundsStats * 8, e->stream));
     if (e->d_fstat)
         HIP_TRY(hipMemsetAsync(e->d_fstat, 0, (size_t)gossip::kFanoutStatLine * gossip::kFanoutStatReplicas * 8, e->stream));
     if (e->d_rbytes) HIP_TRY(hipMemsetAsync(e->d_rbytes, 0, 8, e->stream));

@@ -64,6 +64,8 @@ struct Options {
     double loss = 0.0;                 // ... message-loss probability per made Send
     uint64_t lossSeed = 1;             // ... and the seed of its per-(link, tick) draws
     bool lossSeedGiven = false;
+    uint32_t rounds = 0;               // multi-round push: ticks a node keeps sending a new share (0: not given)
+    bool roundsGiven = false;
     bool uniqueIds = false;            // renumber share ids 1..len in event order (ids are only seen-set keys)
 };
 
@@ -79,7 +81,7 @@ void usage() {
                  "                  [--log=F|-] [--gpus=N] [--shards=S] [--layout=shards|rows]\n"
                  "                  [--memLimitMB=M] [--schedule=exact|philox] [--reach=F]\n"
                  "                  [--fanout=K | --fanoutExact=K] [--fanoutSeed=S] [--uniqueIds]\n"
-                 "                  [--outages=F] [--loss=P] [--lossSeed=S]\n");
+                 "                  [--outages=F] [--loss=P] [--lossSeed=S] [--rounds=R]\n");
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -164,6 +166,11 @@ bool parse(int argc, char** argv, Options& o) {
         }
         else if (key == "outages") { if (!need()) return false; o.outages = val; }
         else if (key == "loss") { if (!num(o.loss) || !(o.loss >= 0.0 && o.loss <= 1.0)) return false; }
+        else if (key == "rounds") {  // (the range is the library's to refuse: gossip_engine_set_rounds)
+            if (!num(d) || d < 0 || d > 4294967295.0 || d != (double)(uint32_t)d) return false;
+            o.rounds = (uint32_t)d;
+            o.roundsGiven = true;
+        }
         else if (key == "uniqueIds") o.uniqueIds = true;
         else {
             std::fprintf(stderr, "unknown option --%s\n", key.c_str());
@@ -240,7 +247,7 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
                 const uint8_t* uid, RowGroup* group, const gossip_topology* topo, const gossip_schedule* sched,
                 const std::vector<double>& per_t, bool link_timing, bool want_trace, double mem_limit_mb,
                 uint32_t fanout, bool fanout_exact, uint64_t fanout_seed, const std::vector<gossip_outage>* outages, uint32_t loss_thr,
-                uint64_t loss_seed, Part& out) {
+                uint64_t loss_seed, const uint32_t* rounds, Part& out) {
     gossip_config cfg = base;
     cfg.device = device;
     if (!rows && count > 1) {
@@ -270,6 +277,7 @@ void run_engine(const gossip_config& base, int device, bool rows, uint32_t rank,
         return fail("fanout", rc);
     if (outages && (rc = gossip_engine_set_outages(eng, outages->size(), outages->data()))) return fail("outages", rc);
     if (loss_thr && (rc = gossip_engine_set_link_loss(eng, loss_thr, loss_seed))) return fail("link loss", rc);
+    if (rounds && (rc = gossip_engine_set_rounds(eng, *rounds))) return fail("rounds", rc);
     for (double t : per_t)  // Start(): p2pnetwork.cc:201-204
         if ((rc = gossip_engine_add_snapshot(eng, gossip_seconds_to_ns(t)))) return fail("snapshot", rc);
     if ((rc = gossip_engine_set_schedule_obj(eng, sched))) return fail("engine schedule", rc);
@@ -454,7 +462,8 @@ int main(int argc, char** argv) {
                 for (uint32_t r = g; r < count; r += ng)
                     run_engine(cfg, o.device + (int)g, rows, r, count, uid.data(), gp, topo, sched, per_t,
                                o.linkTiming, want_trace, o.memLimitMB, o.fanoutExact ? o.fanoutExact : o.fanout, o.fanoutExact != 0, o.fanoutSeed,
-                               o.outages.empty() ? nullptr : &outages, loss_thr, o.lossSeed, parts[r]);
+                               o.outages.empty() ? nullptr : &outages, loss_thr, o.lossSeed, o.roundsGiven ? &o.rounds : nullptr,
+                               parts[r]);
             });
         for (auto& t : th) t.join();
         wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
@@ -473,6 +482,8 @@ int main(int argc, char** argv) {
         if ((o.fanout || o.fanoutExact) && !o.uniqueIds && err.find("unique share ids") != std::string::npos)
             std::fprintf(stderr, "gossip_sim: --fanout%s needs unique share ids: add --uniqueIds to renumber them\n",
                          o.fanoutExact ? "Exact" : "");
+        else if (o.rounds > 1 && !o.uniqueIds && err.find("unique share ids") != std::string::npos)
+            std::fprintf(stderr, "gossip_sim: --rounds needs unique share ids: add --uniqueIds to renumber them\n");
         return 1;
     }
     if (o.hopBatch)

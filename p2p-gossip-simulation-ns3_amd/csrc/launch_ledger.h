@@ -15,7 +15,9 @@
 namespace gossip {
 
 // kernels the ledger records (gossip.h: GOSSIP_K_*)
-enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4, LK_REACH = 5, LK_FANOUT = 6 };
+enum LaunchKernel : uint32_t { LK_PULL = 0, LK_PULL_YOUNG = 1, LK_YOUNG_IDLE = 2, LK_DENSE_BITS = 3, LK_DENSE_DEDUP = 4, LK_REACH = 5, LK_FANOUT = 6, LK_ROUNDS = 7 };
+// FROZEN at the ids 0 .. 6 (the kernels up to the thinning path): the fanout ABI tests pin this line, and
+// nothing sizes an array by it.  It is not the number of ids -- LK_ROUNDS = 7 follows.
 constexpr uint32_t kLaunchKernels = 7;
 
 // k_pull's template flags (gossip.h: GOSSIP_PULL_*)
@@ -84,7 +86,7 @@ struct LaunchRecord {
     uint32_t kernel;   // LaunchKernel
     uint32_t variant;  // k_pull: pull_key; k_pull_young: its bool template argument; k_dense_bits: ksplit;
                        // k_fanout: 1 / 3 / 5 / 6 the count pass (plain, faults, exact, exact with faults), 2 the compact
-                       // pass, 4 the k-th-draw pass; else 0
+                       // pass, 4 the k-th-draw pass; k_rounds: its planes; else 0
     uint64_t launches;
     uint64_t strided;
 };

@@ -68,10 +68,11 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_set_fanout_exact", "gossip_engine_set_fanout_counts", "gossip_fanout_exact_row",
     "gossip_engine_set_outages", "gossip_engine_set_link_loss", "gossip_fault_lost",
     "gossip_engine_get_fault_counters", "gossip_outages_load",
+    "gossip_engine_set_rounds", "gossip_engine_get_rounds_counters",
 )
 
 # launch ledger (gossip.h): kernel ids and k_pull's template flags
-K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP, K_REACH, K_FANOUT = range(7)
+K_PULL, K_PULL_YOUNG, K_YOUNG_IDLE, K_DENSE_BITS, K_DENSE_DEDUP, K_REACH, K_FANOUT, K_ROUNDS = range(8)
 FANOUT_ALWAYS = 0xFFFFFFFF  # forward threshold: probability 1
 PULL_NT, PULL_SP, PULL_PUSH, PULL_SHORT, PULL_FOLD = 1, 2, 4, 8, 16
 
@@ -153,6 +154,13 @@ class gossip_fault_counters(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64), ("down_node_ticks", C.c_uint64), ("lost_copies", C.c_uint64),
         ("down_copies", C.c_uint64), ("dropped_generations", C.c_uint64),
+    ]
+
+
+class gossip_rounds_counters(C.Structure):
+    _fields_ = [
+        ("launches", C.c_uint64), ("resent_bits", C.c_uint64), ("rows_visited", C.c_uint64),
+        ("ms", C.c_double), ("bytes", C.c_uint64),
     ]
 
 
@@ -288,6 +296,8 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_set_link_loss": (C.c_int, [P, u32, u64]),
         "gossip_fault_lost": (C.c_int, [u64, u32, u32, u32, i64, u32]),
         "gossip_engine_get_fault_counters": (C.c_int, [P, C.POINTER(gossip_fault_counters)]),
+        "gossip_engine_set_rounds": (C.c_int, [P, u32]),
+        "gossip_engine_get_rounds_counters": (C.c_int, [P, C.POINTER(gossip_rounds_counters)]),
         "gossip_outages_load": (C.c_int, [u32, i64, C.c_char_p, u64, P, C.POINTER(u64), C.POINTER(u64)]),
         "gossip_engine_destroy": (None, [P]),
         "gossip_format_statistics": (i64, [u32, P, P, P, P, P, P, P, C.c_char_p, u64]),
@@ -716,6 +726,19 @@ class Engine:
     def fault_counters(self) -> gossip_fault_counters:
         c = gossip_fault_counters()
         _check(load_library().gossip_engine_get_fault_counters(self._h, C.byref(c)), "fault counters")
+        return c
+
+    def set_rounds(self, r: int):
+        """Multi-round push (gossip.h, gossip_engine_set_rounds): a node makes Sends of a share in the r ticks
+        from its first contact on, 1 <= r <= 16; 1 switches the feature off.  After the graph, before the
+        schedule, in any order with the fanout and fault setters."""
+        if not 0 <= int(r) <= 0xFFFFFFFF:
+            raise GossipError("set_rounds: rounds: 1 .. 16", E_INVAL)
+        _check(load_library().gossip_engine_set_rounds(self._h, int(r)), "set rounds")
+
+    def rounds_counters(self) -> gossip_rounds_counters:
+        c = gossip_rounds_counters()
+        _check(load_library().gossip_engine_get_rounds_counters(self._h, C.byref(c)), "rounds counters")
         return c
 
     def set_schedule(self, ev: np.ndarray):
