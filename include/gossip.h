@@ -503,6 +503,21 @@ typedef struct gossip_rounds_counters {
 } gossip_rounds_counters;
 /* Since the last gossip_engine_reset_timing; all zero on an engine without rounds (r = 1). */
 int gossip_engine_get_rounds_counters(gossip_engine* e, gossip_rounds_counters* c);
+/* Read-back of the thinned peer lists (tests, debugging): the lists the last finished tick made.  *tick is
+ * that tick T: row v holds the distinct peers u with a Send u -> v of T that was made and arrives (selected,
+ * not lost, v up in T + 1), and the pull of T + 1 walks them.  row_ptr (n + 1, may be NULL) and col are a
+ * CSR; the order of a row's peers is the engine's own (the order of its full peer list).  bound (n, may be
+ * NULL) is exact-k mode's per-node table of the tick: the k[u]-th smallest draw of a node that selects,
+ * 2^64 - 1 of a node that sends every copy, without meaning at k[u] = 0; a non-NULL bound in another mode is
+ * GOSSIP_EINVAL.  *num_entries = row_ptr[n] is always written; if col is not NULL and col_cap is smaller,
+ * the call returns GOSSIP_EINVAL after writing it (query with col = NULL, then fetch, as
+ * gossip_engine_get_launches).  GOSSIP_ESTATE on an engine that thins no lists (no fanout, fault or rounds
+ * setter), before the first tick has finished, and between gossip_engine_tick_begin and _tick_end.  The
+ * call synchronises the engine stream and copies: it launches nothing, allocates nothing on the device and
+ * changes no counter, no ledger record and not device_bytes. */
+int gossip_engine_get_thinned_lists(gossip_engine* e, int64_t* tick, int64_t* row_ptr /* n + 1, or NULL */,
+                                    int32_t* col, uint64_t col_cap, uint64_t* num_entries,
+                                    uint64_t* bound /* n, or NULL */);
 /* Tuning options of one engine (results never depend on them; A/B runs and tests).  The
  * environment variable in brackets gives the default:
  *   "pull_nt"          -1 auto (non-temporal rows when the live frontier n x wact x 8 B exceeds

@@ -1048,6 +1048,7 @@ struct gossip_engine {
     int64_t opt_fanout_grid = 0;       // blocks of the two passes, 0 = auto
     bool forced_young_idle = false;    // set_option("young_idle", 1) was called
     uint64_t fanout_launches = 0;
+    int64_t thinned_tick = INT64_MIN;  // the last tick fanout_launch thinned (gossip_engine_get_thinned_lists)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_fanout;
     double fanout_ms_done = 0.0;
     int fanout_launch(int64_t t);      // tick_step_b: the selection of tick t, for the pull of t + 1
@@ -3964,6 +3965,7 @@ int gossip_engine::fanout_launch(int64_t t) {
         timers_fanout.emplace_back(e0, e1);
     }
     fanout_launches++;
+    thinned_tick = t;
     return GOSSIP_OK;
 }
 
@@ -5108,6 +5110,30 @@ int gossip_engine_get_fanout_counters(gossip_engine* e, gossip_fanout_counters* 
     // copies and no sent (4 + 16 + 8 + 16 per node)
     if (e->fanout_exact)
         c->bytes += e->fanout_launches * (n * 64 + e->exact_drawn * 5 + nnz * 8) - e->fanout_launches * (nnz * 4 + n * 44);
+    return GOSSIP_OK;
+}
+
+// The thinned lists of the last finished tick, copied as they lie on the device: a stream synchronisation and
+// copies -- no launch, no allocation, no counter.
+int gossip_engine_get_thinned_lists(gossip_engine* e, int64_t* tick, int64_t* row_ptr, int32_t* col, uint64_t col_cap,
+                                    uint64_t* num_entries, uint64_t* bound) {
+    if (!e || !tick || !num_entries) return set_error(GOSSIP_EINVAL, "NULL argument");
+    if (!e->fanout) return set_error(GOSSIP_ESTATE, "thinned lists: the engine thins no peer lists (no fanout, fault or rounds setter ran)");
+    if (e->tick_open) return set_error(GOSSIP_ESTATE, "thinned lists: not between tick_begin and tick_end");
+    if (e->thinned_tick == INT64_MIN) return set_error(GOSSIP_ESTATE, "thinned lists: no tick has finished yet");
+    if (bound && !e->fanout_exact) return set_error(GOSSIP_EINVAL, "thinned lists: bounds exist in exact-k mode only");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    int64_t total = 0;
+    HIP_TRY(hipMemcpy(&total, e->d_rowptr_t + e->n, 8, hipMemcpyDeviceToHost));
+    *tick = e->thinned_tick;
+    *num_entries = (uint64_t)total;
+    if (total < 0 || (uint64_t)total > e->nnz) return set_error(GOSSIP_EHIP, "thinned lists: row pointers out of range");
+    if (col && col_cap < (uint64_t)total)
+        return set_error(GOSSIP_EINVAL, "thinned lists: " + std::to_string(total) + " entries, room for " + std::to_string(col_cap));
+    if (row_ptr) HIP_TRY(hipMemcpy(row_ptr, e->d_rowptr_t, ((size_t)e->n + 1) * 8, hipMemcpyDeviceToHost));
+    if (col && total) HIP_TRY(hipMemcpy(col, e->d_col_t, (size_t)total * 4, hipMemcpyDeviceToHost));
+    if (bound && e->n) HIP_TRY(hipMemcpy(bound, e->d_xbound, (size_t)e->n * 8, hipMemcpyDeviceToHost));
     return GOSSIP_OK;
 }
 

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "gossip_engine_set_outages", "gossip_engine_set_link_loss", "gossip_fault_lost",
     "gossip_engine_get_fault_counters", "gossip_outages_load",
     "gossip_engine_set_rounds", "gossip_engine_get_rounds_counters",
+    "gossip_engine_get_thinned_lists",
 )
 
 # launch ledger (gossip.h): kernel ids and k_pull's template flags
@@ -298,6 +299,7 @@ def load_library(path: str = LIB_PATH):
         "gossip_engine_get_fault_counters": (C.c_int, [P, C.POINTER(gossip_fault_counters)]),
         "gossip_engine_set_rounds": (C.c_int, [P, u32]),
         "gossip_engine_get_rounds_counters": (C.c_int, [P, C.POINTER(gossip_rounds_counters)]),
+        "gossip_engine_get_thinned_lists": (C.c_int, [P, C.POINTER(i64), P, P, u64, C.POINTER(u64), P]),
         "gossip_outages_load": (C.c_int, [u32, i64, C.c_char_p, u64, P, C.POINTER(u64), C.POINTER(u64)]),
         "gossip_engine_destroy": (None, [P]),
         "gossip_format_statistics": (i64, [u32, P, P, P, P, P, P, P, C.c_char_p, u64]),
@@ -740,6 +742,21 @@ class Engine:
         c = gossip_rounds_counters()
         _check(load_library().gossip_engine_get_rounds_counters(self._h, C.byref(c)), "rounds counters")
         return c
+
+    def thinned_lists(self, bound: bool = False):
+        """The thinned peer lists the last finished tick made (gossip.h, gossip_engine_get_thinned_lists):
+        (tick, row_ptr, col), and with bound=True exact-k mode's per-node bounds as a fourth item."""
+        lib = load_library()
+        tick, total = C.c_int64(), C.c_uint64()
+        _check(lib.gossip_engine_get_thinned_lists(self._h, C.byref(tick), None, None, 0, C.byref(total), None), "thinned lists")
+        row_ptr = np.empty(self.n + 1, np.int64)
+        col = np.empty(total.value, np.int32)
+        bd = np.empty(self.n, np.uint64) if bound else None
+        # (a buffer is passed even when empty: a NULL bound means "not asked for")
+        _check(lib.gossip_engine_get_thinned_lists(self._h, C.byref(tick), C.c_void_p(row_ptr.ctypes.data), C.c_void_p(col.ctypes.data),
+                                                   col.size, C.byref(total), C.c_void_p(bd.ctypes.data) if bound else None),
+               "thinned lists")
+        return (tick.value, row_ptr, col, bd) if bound else (tick.value, row_ptr, col)
 
     def set_schedule(self, ev: np.ndarray):
         ev = np.ascontiguousarray(ev, GEN_EVENT_DTYPE)

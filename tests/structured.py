@@ -68,6 +68,26 @@ def components(n1=130, n2=70, isolated=3):
             np.concatenate([b1, b2 + n1]).astype(np.uint32))
 
 
+def gaps(n1=100, empty=130, n2=103):
+    """ring_chords(n1, 7), then `empty` peerless nodes, then ring_chords(n2, 7): n = 333.  For the kernels that
+    walk 64-node chunks of the flat entry range: the chunk of nodes 128 .. 191 has no entries and starts inside
+    a 64-entry word (rowptr & 63 != 0), chunk 64 .. 127 ends in empty rows and chunk 192 .. 255 begins with them."""
+    _, a1, b1 = ring_chords(n1, 7)
+    _, a2, b2 = ring_chords(n2, 7)
+    off = n1 + empty
+    return (off + n2, np.concatenate([a1, a2 + off]).astype(np.uint32), np.concatenate([b1, b2 + off]).astype(np.uint32))
+
+
+# ring_chords(n, 0) at these n: every node has degree 2, so every 64-node chunk starts on a 64-entry word
+# boundary (rowptr & 63 == 0) and only the last word of the flat entry range is covered in part
+ALIGNED_RING_N = (129, 513)
+
+
+def aligned_ring(n):
+    assert n in ALIGNED_RING_N
+    return ring_chords(n, 0)
+
+
 def events(n, ticks, per_tick, seed, id_mask=0, must_include=()):
     """per_tick distinct nodes generate in each of `ticks` ticks of L = 5 ms after T0 (a node has at
     most one birth per tick), node v always at its own phase in [1, L), all phases distinct; sorted

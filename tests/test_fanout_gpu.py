@@ -22,6 +22,7 @@ import pytest
 
 import fanout_ref as F
 import structured as S
+import thinning_ref as TH
 from cases import L, T0
 
 pytestmark = pytest.mark.gpu
@@ -138,8 +139,21 @@ def _run(gossip, topo, ev, t_cut, what, k=None, thr=None, seed=1, trace=True, **
     _same(got, want, what, trace)
     f, c = got["fanout"], got["counters"]
     assert f.launches == c.ticks > 0 and f.entries == c.ticks * int(topo.csr()[0][-1]), what
-    assert f.selected_out >= int(want["sent"].sum() > 0) and f.bytes > 0, what
+    assert f.bytes > 0, what
+    _same_totals(got, topo, what, thr=_thr(topo, k) if k is not None else thr, seed=seed)
     return got
+
+
+def _same_totals(got, topo, what, **config):
+    """The kernels' own totals against the model of the thinned lists (thinning_ref.py), summed over the ticks the
+    run executed: every tick thins every list, whether or not a share is on it."""
+    first = T0 // L  # gossip_engine_first_tick of every engine here
+    want = TH.of_topology(topo, **config).totals(range(first, first + int(got["counters"].ticks)))
+    f = got["fanout"]
+    assert (f.selected_in, f.selected_out) == (want["selected_in"], want["selected_out"]), (what, want)
+    if "faults" in got:
+        x = got["faults"]
+        assert (x.lost_copies, x.down_copies, x.down_node_ticks) == (want["lost_copies"], want["down_copies"], want["down_node_ticks"]), (what, want)
 
 
 def _pull_keys(res, gossip):

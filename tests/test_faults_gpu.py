@@ -14,6 +14,7 @@ import pytest
 import fanout_ref as F
 import faults_ref as R
 import structured as S
+import thinning_ref as TH
 from cases import L, T0
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +153,13 @@ def _run(gossip, topo, ev, t_cut, what, outages=(), loss_thr=0, loss_seed=1, k=N
         assert got["fanout"].launches == f.launches, what  # the thinning passes of a faults-only engine are reported
     else:
         assert (f.launches, f.down_node_ticks, f.lost_copies, f.down_copies) == (0, 0, 0, 0) and 3 not in rec, what
+    # the totals of the thinning passes: the model of the thinned lists (thinning_ref.py), over the ticks of the run
+    tot = TH.of_topology(topo, thr=thr if k is not None else None, seed=fan_seed, outages=tuple(outages), loss_thr=loss_thr,
+                         loss_seed=loss_seed).totals(range(first, first + int(got["counters"].ticks)))
+    fo = got["fanout"]
+    assert fo.launches == got["counters"].ticks, what
+    assert (fo.selected_in, fo.selected_out) == (tot["selected_in"], tot["selected_out"]), (what, tot)
+    assert (f.down_node_ticks, f.lost_copies, f.down_copies) == (tot["down_node_ticks"], tot["lost_copies"], tot["down_copies"]), what
     return got, want
 
 

@@ -17,6 +17,7 @@ import fanout_ref as F
 import faults_ref as R
 import rounds_ref as M
 import structured as S
+import thinning_ref as TH
 from cases import L, T0
 
 pytestmark = pytest.mark.gpu
@@ -161,6 +162,13 @@ def _run(gossip, topo, ev, t_cut, r, what, mode=None, seed=1, outages=(), loss_t
     assert len(rec) == 1 and rec[0].arg == M.planes(r) and rec[0].launches == rc.launches > 0, what
     assert rc.rows_visited > 0 and rc.bytes >= 16 * rc.rows_visited, what
     assert got["faults"].dropped_generations == want["dropped"], what
+    # the totals of the thinning passes: the model of the thinned lists (rounds do not enter the selection)
+    first, fo, fa = got["ticks"][0], got["fanout"], got["faults"]
+    tot = TH.of_topology(topo, seed=seed, outages=tuple(outages), loss_thr=loss_thr, loss_seed=loss_seed,
+                         **_model_kw(topo, mode)).totals(range(first, first + int(got["counters"].ticks)))
+    assert fo.launches == got["counters"].ticks, what
+    assert (fo.selected_in, fo.selected_out) == (tot["selected_in"], tot["selected_out"]), (what, tot)
+    assert (fa.lost_copies, fa.down_copies, fa.down_node_ticks) == (tot["lost_copies"], tot["down_copies"], tot["down_node_ticks"]), what
     return got, want
 
 
